@@ -12,6 +12,12 @@ products y = A x on the resident matrix (halo exchange included when N > 1) -- a
 work, so that the K timed steps are not a 2 ms window.  Inputs are resident in HBM before the
 timed region.
 
+A plain run does only what `value` needs: set-up, W warm-up steps, the K timed steps and the line
+(`ms_per_step` = wall time of one timed step).  `--full` adds everything else the line used to carry
+(self-checks, per-launch roofline figures, CG, the other configs, ceilings, CPU baselines).
+`--dump-outputs DIR` writes y of the last timed product to DIR/y.npy; the inputs are the same on
+every run, so two builds can be compared output for output.
+
 Accounting.  `value` and `roofline.achieved` count the bytes the running kernel
 MOVES by construction -- its stored format as it reads it (sgm_mat_footprint: padded slices,
 codes, row pointers) + every x entry once + every y entry once -- divided by wall time / by the
@@ -35,6 +41,8 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0       # MI355X_MICROARCH.md: HBM3E 8 TB/s spec (about 6.3 TB/s achievable)
 PROFILE_TAG = "r06"
+DUMP_MAX_ROWS = 1 << 22     # --dump-outputs: at most 32 MiB of float64
+DUMP_SEED = 0
 
 
 def spmv_bytes(n, m, nnz):
@@ -54,8 +62,15 @@ def csrc_sha1():
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: the self-checks of the products, per-launch HIP-event "
+                         "timing (roofline), the other CSR kernels, CG, the C1 / C3 / C4 / C5 legs, time to solution, the "
+                         "stream ceilings and the CPU baselines (the --no-* switches below select among these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write y of the last product (rank 0's rows, float64) to DIR/y.npy; above "
+                         f"{DUMP_MAX_ROWS} rows a fixed sample of rows (seed {DUMP_SEED}, ascending)")
     ap.add_argument("--spmv-per-step", type=int, default=512,
                     help="products y = A x per timed step (one step is about 50 ms of GPU work)")
     ap.add_argument("--nx", type=int, default=3162)
@@ -96,7 +111,10 @@ def parse_args():
     ap.add_argument("--deadline-s", type=float, default=1500.0,
                     help="whole-run limit: a rank past it prints where it is and exits 86; with `--gpus N` typed plainly the "
                          "parent also kills its children (by PID) then and prints every rank's last phase")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ------------------------------------------------------------------------------------------ #
@@ -460,8 +478,9 @@ def worker(args):
         return its, dtc, res2, phases
 
     # ---- N = 1: what a plain streaming kernel reaches on THIS GPU today (tools/stream_bench, a child process) --------------
+    full = args.full
     ceilings = None
-    if rank == 0 and world == 1 and not use_dist and not args.no_ceilings and args.workload == "c2":
+    if full and rank == 0 and world == 1 and not use_dist and not args.no_ceilings and args.workload == "c2":
         hb.phase("stream ceilings: tools/stream_bench at 600 and 7600 MiB")
         ceilings = stream_ceilings()
 
@@ -472,12 +491,14 @@ def worker(args):
     resident_rank, moved_rank = A.footprint()
     inner = max(1, args.spmv_per_step)
 
-    hb.phase(f"{args.workload}: first product + self-check against the stored-order row sums")
+    hb.phase(f"{args.workload}: first product" + (" + self-check against the stored-order row sums" if full else ""))
     A.matvec(x, y)
     torch.cuda.synchronize()
-    check_main = selfcheck(args.workload, y, n_loc, i0)
-    if not check_main:
-        sys.stderr.write(f"[bench] rank {rank}: the product differs from its row sums in stored order -- not a measurement\n")
+    check_main = None
+    if full:
+        check_main = selfcheck(args.workload, y, n_loc, i0)
+        if not check_main:
+            sys.stderr.write(f"[bench] rank {rank}: the product differs from its row sums in stored order -- not a measurement\n")
     hb.phase(f"{args.workload}: {args.warmup} warm-up steps of {inner} products")
     for _ in range(args.warmup):
         for _ in range(inner):
@@ -497,6 +518,47 @@ def worker(args):
     alg_all = sum_over_ranks(alg_bytes_rank)
     value = moved_all * launches / dt / 1e9
     effective = alg_all * launches / dt / 1e9
+    if args.dump_outputs and rank == 0:
+        hb.phase(f"{args.workload}: writing y of the last timed product to {args.dump_outputs}")
+        dump_outputs(args.dump_outputs, y, n_loc)
+
+    def teardown():
+        hb.phase("teardown")
+        if use_dist:
+            barrier()
+            comm.destroy()
+            dist.destroy_process_group()
+        hb.finish()
+
+    head = {
+        "metric": "SpMV GB/s (achieved HBM) + CG iters/sec on 5-pt Laplacian, N=1e7",
+        "value": value, "unit": "GB/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step, "higher_is_better": True,
+        "scaling": "weak" if args.workload == "c2" else "strong", "vs_baseline": None,
+        "dtype": "f64", "data": "synthetic",
+        "config": {"workload": f"{label} (rank 0: n={n_loc}, nnz={nnz}), fp64 SpMV y=A*x",
+                   "spmv_per_step": inner, "rows_per_gpu": n_loc, "nnz_per_gpu": int(nnz),
+                   "parallelism": f"row-partition x{world}",
+                   "cg_dist_halo_fused": halo_mode if use_dist else None, "rccl_group_probe": group_probe,
+                   "matrix_resident_bytes_per_gpu": resident_rank,
+                   "reference_layout_bytes_per_gpu": 12 * nnz + 4 * (n_loc + 1),
+                   "value_counts": "bytes the kernel moves by construction (stored format + x + y), not the reference layout's",
+                   "full": full},
+        "effective_GBs_on_reference_bytes": effective,
+    }
+    if not full:
+        if rank == 0:
+            per_gpu = value / world
+            head["roofline"] = {"bound": "hbm", "achieved": per_gpu, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                "frac": per_gpu / HBM_PEAK_GBS, "kernel": A.kernel, "moved_bytes_per_launch": moved_rank,
+                                "note": "plain run: achieved = the timed steps' moved bytes / their wall time, per GPU; --full "
+                                        "adds the per-launch HIP-event figures, traffic, the self-checks and the other legs"}
+            json_out.write(json.dumps(head) + "\n")
+            json_out.flush()
+        A.destroy()
+        del x, y
+        teardown()
+        return
 
     # ---- dominant kernel with HIP events on the launch stream -------------------------------
     hb.phase(f"{args.workload}: per-launch HIP-event timing (warm and cold)")
@@ -674,19 +736,7 @@ def worker(args):
 
     if rank == 0:
         out = {
-            "metric": "SpMV GB/s (achieved HBM) + CG iters/sec on 5-pt Laplacian, N=1e7",
-            "value": value, "unit": "GB/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step, "higher_is_better": True,
-            "scaling": "weak" if args.workload == "c2" else "strong", "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic",
-            "config": {"workload": f"{label} (rank 0: n={n_loc}, nnz={nnz}), fp64 SpMV y=A*x",
-                       "spmv_per_step": inner, "rows_per_gpu": n_loc, "nnz_per_gpu": int(nnz),
-                       "parallelism": f"row-partition x{world}",
-                       "cg_dist_halo_fused": halo_mode if use_dist else None, "rccl_group_probe": group_probe,
-                       "matrix_resident_bytes_per_gpu": resident_rank,
-                       "reference_layout_bytes_per_gpu": 12 * nnz + 4 * (n_loc + 1),
-                       "value_counts": "bytes the kernel moves by construction (stored format + x + y), not the reference layout's"},
-            "effective_GBs_on_reference_bytes": effective,
+            **head,
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, **flat,
                          "kernel": main_kernel, "moved_bytes_per_launch": moved_rank,
@@ -711,12 +761,7 @@ def worker(args):
         }
         json_out.write(json.dumps(out) + "\n")
         json_out.flush()
-    hb.phase("teardown")
-    if use_dist:
-        barrier()
-        comm.destroy()
-        dist.destroy_process_group()
-    hb.finish()
+    teardown()
     if not check_main or (c5 is not None and not c5["product_bit_exact_on_every_rank"]) or \
             any(leg is not None and not leg["product_bit_exact"] for leg in (c3, c4)):
         sys.exit(3)          # a product that differs is not a measurement
@@ -736,6 +781,19 @@ def spmv_fracs(t, moved, survey):
            "frac_survey_bytes": (survey / t / 1e9 / HBM_PEAK_GBS) if moved >= survey else None,
            "layout_compression": survey / moved}
     return out
+
+
+def dump_outputs(d, y, n_loc):
+    """--dump-outputs: y of the last timed product as d/y.npy, float64.  Above DUMP_MAX_ROWS rows, the rows of a fixed sample
+    (seed DUMP_SEED, ascending), so that every run writes the same rows and the file stays within 32 MiB."""
+    import numpy as np
+    import torch
+    os.makedirs(d, exist_ok=True)
+    y = y[:n_loc]
+    if n_loc > DUMP_MAX_ROWS:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n_loc, DUMP_MAX_ROWS, replace=False))
+        y = y[torch.from_numpy(rows).to(y.device)]
+    np.save(os.path.join(d, "y.npy"), y.cpu().numpy().astype(np.float64))
 
 
 def timed_launches(torch, fn, reps, warm=3):

@@ -331,6 +331,42 @@ def test_header_is_c99_and_a_plain_c_program_links_and_fails_loudly_without_a_gp
     assert "sgm_init" in p.stderr and "no CPU path" in p.stderr, p.stderr
 
 
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_bench_refuses_zero_timed_steps():
+    """`--steps` is the number of timed steps and `ms_per_step` is divided by it: 0 is refused before anything starts."""
+    import subprocess
+    import sys
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 2 and "--steps must be at least 1" in p.stderr, (p.returncode, p.stderr)
+    assert p.stdout.strip() == ""
+
+
+def test_bench_dump_outputs_are_the_same_rows_on_every_run(tmp_path):
+    """--dump-outputs: y as float64; above DUMP_MAX_ROWS rows a fixed, ascending sample of rows, the same on every run."""
+    import torch
+    bench = _bench_module()
+    small = torch.arange(1000, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "s"), small, 1000)
+    got = np.load(str(tmp_path / "s" / "y.npy"))
+    assert got.dtype == np.float64 and np.array_equal(got, small.numpy())
+    n = bench.DUMP_MAX_ROWS + 12345
+    y = torch.arange(n, dtype=torch.float64) * 0.5
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), y, n)
+    a, b = np.load(str(tmp_path / "a" / "y.npy")), np.load(str(tmp_path / "b" / "y.npy"))
+    assert a.dtype == np.float64 and a.shape == (bench.DUMP_MAX_ROWS,) and a.nbytes <= 64 << 20
+    assert np.array_equal(a, b)
+    rows = a / 0.5
+    assert np.all(np.diff(rows) > 0) and rows[0] >= 0 and rows[-1] < n
+
+
 def test_bench_flat_keys_fit_the_drivers_record():
     """The driver keeps the first 24 scalars of `roofline` (6 are bound..traffic): the 18 after them must be the one-per-graded-
     thing list of VERDICT r05 item 1, whatever else the legs emit (r05's record lost C3 / C4 / cold / in-solver to new keys)."""

@@ -177,7 +177,7 @@ def test_bench_gpus_2_typed_plainly_spawns_its_ranks(tmp_path):
     env.update({"SGM_RCCL_LIB": MOCK, "SGM_BENCH_SAME_GPU": "1"})
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1",
                         "--spmv-per-step", "4", "--nx", "300", "--ny", "200", "--cg-steps", "20", "--c5-edge", "40",
                         "--c5-cg-steps", "10", "--no-cpu"], env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -203,7 +203,7 @@ def test_bench_gpus_8_runs_end_to_end_before_a_node_does(launcher, tmp_path):
     env.update({"SGM_RCCL_LIB": MOCK, "SGM_BENCH_SAME_GPU": "1"})
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(k, None)
-    bench_args = [os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--spmv-per-step", "4",
+    bench_args = [os.path.join(ROOT, "bench.py"), "--full", "--gpus", "8", "--steps", "2", "--warmup", "1", "--spmv-per-step", "4",
                   "--nx", "300", "--ny", "200", "--cg-steps", "20", "--c5-edge", "96", "--c5-cg-steps", "10", "--no-cpu"]
     if launcher == "plain":
         cmd = [sys.executable] + bench_args
@@ -255,7 +255,7 @@ def test_bench_with_a_second_communicator_for_the_halo(tmp_path):
     env.update({"SGM_RCCL_LIB": MOCK, "SGM_BENCH_SAME_GPU": "1"})
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1",
                         "--spmv-per-step", "4", "--nx", "300", "--ny", "200", "--cg-steps", "20", "--c5-edge", "40",
                         "--c5-cg-steps", "10", "--no-cpu", "--halo-comm"], env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -272,7 +272,7 @@ def test_dist_overhead_leg_runs_the_rccl_path_with_one_rank(tmp_path):
     env.update({"SGM_RCCL_LIB": MOCK})
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--spmv-per-step", "4",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--spmv-per-step", "4",
                         "--nx", "300", "--ny", "200", "--cg-steps", "20", "--no-c5", "--no-cpu", "--no-variants"], env=env,
                        capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -281,6 +281,33 @@ def test_dist_overhead_leg_runs_the_rccl_path_with_one_rank(tmp_path):
     assert "error" not in d, d
     assert d["iterations"] == 20 and d["iters_per_s_dist_path"] > 0 and d["iters_per_s_plain_path"] > 0
     assert 2.0 <= d["phases"]["allreduce"]["events_per_iter"] <= 2.2 and d["phases"]["halo_post_to_done"]["events_per_iter"] == 0
+
+
+def test_plain_bench_line_and_its_dumped_outputs(tmp_path):
+    """A plain run (no --full): the timed steps' figures only, `--steps` of them, and --dump-outputs writes y of the last
+    product -- the same bits on a second run, and within rounding of sin(0.001 i) of the oracle's product of that x."""
+    import numpy as np
+    import oracle as orc
+    from sigma_amd import problems as P
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    ys = []
+    for k in range(2):
+        d = tmp_path / f"out{k}"
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--spmv-per-step", "4",
+                            "--nx", "300", "--ny", "200", "--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(line) == 1, p.stdout[-2000:]
+        out = json.loads(line[0])
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0 and out["unit"] == "GB/s"
+        assert out["config"]["full"] is False and "cg" not in out and "selfcheck" not in out
+        ys.append(np.load(str(d / "y.npy")))
+    n = 300 * 200
+    assert ys[0].dtype == np.float64 and ys[0].shape == (n,)
+    assert np.array_equal(ys[0], ys[1])
+    ptr, node, val = P.poisson2d_csr(300, 200)
+    ref = orc.CsrMatrix(n, n, ptr, node, val).matvec(np.sin(0.001 * np.arange(1, n + 1, dtype=np.float64)))
+    assert np.abs(ys[0] - ref).max() <= 1e-13
 
 
 def test_bench_under_torch_distributed_run_like_the_driver_launches_it(tmp_path):
@@ -292,7 +319,7 @@ def test_bench_under_torch_distributed_run_like_the_driver_launches_it(tmp_path)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-                        "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps",
+                        "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps",
                         "2", "--warmup", "1", "--spmv-per-step", "4", "--nx", "300", "--ny", "200", "--cg-steps", "20",
                         "--c5-edge", "40", "--c5-cg-steps", "10", "--no-cpu"], env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -314,7 +341,7 @@ def test_a_rank_stuck_in_the_halo_exchange_is_named_and_the_run_ends(launcher, t
     env.update({"SGM_RCCL_LIB": MOCK, "SGM_BENCH_SAME_GPU": "1", "MOCK_RCCL_STALL": "1:12"})
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(k, None)
-    bench_args = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--spmv-per-step", "40",
+    bench_args = [os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--spmv-per-step", "40",
                   "--nx", "300", "--ny", "200", "--cg-steps", "20", "--c5-edge", "40", "--c5-cg-steps", "10", "--no-cpu",
                   "--stall-s", "8", "--deadline-s", "200"]
     if launcher == "plain":

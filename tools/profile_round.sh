@@ -4,14 +4,14 @@ cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/prof_round
 rm -rf $OUT; mkdir -p $OUT
-T0=$(date +%s); timeout 900 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo bench=$? wall=$(( $(date +%s) - T0 ))s | tee $OUT/bench_wall.txt
-BARGS="--steps 2 --warmup 1 --spmv-per-step 64 --cg-steps 30 --no-cpu --no-c5 --no-c3 --no-c4 --no-dist-overhead --no-pcg --no-ceilings"
+T0=$(date +%s); timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo bench=$? wall=$(( $(date +%s) - T0 ))s | tee $OUT/bench_wall.txt
+BARGS="--full --steps 2 --warmup 1 --spmv-per-step 64 --cg-steps 30 --no-cpu --no-c5 --no-c3 --no-c4 --no-dist-overhead --no-pcg --no-ceilings"
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 bench.py $BARGS > $OUT/stats.log 2>&1
-PARGS="--steps 1 --warmup 1 --spmv-per-step 4 --cg-steps 0 --no-cpu --no-c5 --no-c3 --no-c4 --no-variants --no-dist-overhead --no-pcg --no-ceilings"
+PARGS="--full --steps 1 --warmup 1 --spmv-per-step 4 --cg-steps 0 --no-cpu --no-c5 --no-c3 --no-c4 --no-variants --no-dist-overhead --no-pcg --no-ceilings"
 timeout 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- python3 bench.py $PARGS > $OUT/pmc1.log 2>&1
 timeout 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -- python3 bench.py $PARGS > $OUT/pmc2.log 2>&1
 # HBM bytes of the CG update kernels (k_elem<FCgR / FCgPX>) and of the C5 product (k_csr_sl<7>, 464^3): their own PMC passes
-QARGS="--steps 1 --warmup 1 --spmv-per-step 2 --cg-steps 10 --c5-cg-steps 4 --no-cpu --no-c3 --no-c4 --no-variants --no-dist-overhead --no-pcg --no-ceilings --no-c5-parts"
+QARGS="--full --steps 1 --warmup 1 --spmv-per-step 2 --cg-steps 10 --c5-cg-steps 4 --no-cpu --no-c3 --no-c4 --no-variants --no-dist-overhead --no-pcg --no-ceilings --no-c5-parts"
 timeout 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch_cg_c5 -- python3 bench.py $QARGS > $OUT/pmc3.log 2>&1
 timeout 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write_cg_c5 -- python3 bench.py $QARGS > $OUT/pmc4.log 2>&1
 # ILDU(0)-PCG on the 1000^2 grid: per-kernel times of the triangular solves
@@ -57,7 +57,7 @@ cat $OUT/bench.json | cut -c1-600
 # the bench line once more, now that this round's PMC passes exist: condense them on the box (profiles/r03/pmc_hbm_traffic.json
 # with the fingerprint of the sources that just ran) so that `roofline.traffic` of the line is this run's own figure
 python tools/collect_profiles.py ${TAG:-r06} > /dev/null 2>&1
-timeout 900 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo bench_with_traffic=$?
+timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo bench_with_traffic=$?
 # what travels back is capped at 64 MiB: the per-dispatch traces are not needed once the stats exist
 find $OUT -name "*kernel_trace.csv" -delete
 du -sh $OUT
