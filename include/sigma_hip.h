@@ -232,6 +232,26 @@ int sgm_csr_from_edges(sgm_mat *out, int32_t nrow, int32_t ncol, int64_t ne, con
 int sgm_ell_from_edges(sgm_mat *out, int32_t nrow, int32_t ncol, int64_t ne, const int32_t *ei_1based,
                        const int32_t *ej_1based, const double *ev, int where);
 int sgm_mat_get(sgm_mat A, const char *name, void *out_host, size_t bytes, size_t *needed);
+/* ---- sparse matrix algebra (src/matrix/sparse_matrix_algebra.f90:13) ------------------ *
+ * sgm_mat_sum     <- sparse_matrix_sum      sparse_matrix_algebra.f90:25-145   A = B + C
+ * sgm_mat_product <- sparse_matrix_product  :154-189 -> sparse_matrix_product_C :310-420   A = B * C
+ * sgm_mat_ptap    <- PtAP                   :425-538   B = P^T A P
+ * sgm_mat_rart    <- RARt                   :543-655   B = R A R^T
+ * The result is a new single-GPU CSR leaf (*out), bit-identical to the reference's: the columns of every
+ * row in the order of their first contribution (ll_graphs.f90:355-370, cs_graphs.f90:109-197), every
+ * value +0.0 plus its terms in contribution order (cs_matrices.f90:868-891), each term a product rounded
+ * on its own.  Operands are single-GPU CSR leaves; composite, distributed / partitioned and ELLPACK
+ * operands are SGM_ERR_UNSUPPORTED; shapes that do not fit are SGM_ERR_DIMS (the reference exits).
+ * The result keeps its symbolic plan (freed by sgm_mat_destroy).  sgm_mat_get(out, "algebra_rows")
+ * reads {rows its symbolic pass ran in LDS, rows that took the long-row path}.
+ * sgm_mat_algebra_refill(out, X, Y): only the values again, from the operands' current values (the
+ * same handles in the same order as at creation, none of the three permuted since; else
+ * SGM_ERR_BAD_ARG); bumps out's version like sgm_csr_set_values.                            */
+int sgm_mat_sum(sgm_mat *out, sgm_mat B, sgm_mat C);       /* A = B + C   */
+int sgm_mat_product(sgm_mat *out, sgm_mat B, sgm_mat C);   /* A = B * C   */
+int sgm_mat_ptap(sgm_mat *out, sgm_mat A, sgm_mat P);      /* B = P^T A P */
+int sgm_mat_rart(sgm_mat *out, sgm_mat A, sgm_mat R);      /* B = R A R^T */
+int sgm_mat_algebra_refill(sgm_mat out, sgm_mat X, sgm_mat Y);
 /* sgm_composite_create <- type(sparse_matrix), the block "matrix of matrices"
  *                         src/matrix/sparse_matrix_composites.f90:41-162; matvec_add = loop over
  *                         the blocks `C%matvec_add(x(j1:j2), y(i1:i2))`, :1076-1099 (row blocks

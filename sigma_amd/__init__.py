@@ -6,6 +6,8 @@ hot path -- same names, argument meaning and error behaviour --
 
     A = csr_matrix(n, m, ptr, node, val)       cs_matrices.f90:32-151  (1-based arrays)
     A = ellpack_matrix(n, m, node, val)        ellpack_matrices.f90:28-105
+    sparse_matrix_sum(B, C), sparse_matrix_product(B, C), PtAP(A, P), RARt(A, R)
+                                               sparse_matrix_algebra.f90:13; result.refill(X, Y)
     A.matvec(x, y); A.matvec_add(x, y)         linear_operator_interface.f90:185-194
     solver = cg(tolerance)                     cg_solvers.f90:36-47
     solver = bicgstab(tolerance)               bicgstab_solvers.f90:37-48
@@ -392,6 +394,49 @@ class csr_matrix(_Matrix):
     def set_values(self, val):
         pv, w, _k = _arg(val, np.float64)
         _ck(lib().sgm_csr_set_values(self._h, pv, C.c_int(w)))
+
+
+    # -- sparse_matrix_algebra.f90: the result of sparse_matrix_sum / sparse_matrix_product / PtAP / RARt ----
+    def refill(self, X, Y):
+        """Recompute only the values of this result from the operands' current values (sgm_mat_algebra_refill): X, Y are
+        the handles it was built from, in the same order; none of the three may have been permuted since."""
+        _ck(lib().sgm_mat_algebra_refill(self._h, X._h, Y._h))
+        return self
+
+    def algebra_rows(self):
+        """(rows whose symbolic pass ran in LDS, rows that took the long-row path) of a matrix algebra result."""
+        r = self.get("algebra_rows", np.int32)
+        return int(r[0]), int(r[1])
+
+
+def _algebra(fn, X, Y):
+    M = csr_matrix.__new__(csr_matrix)
+    _Matrix.__init__(M)
+    _ck(fn(C.byref(M._h), X._h, Y._h))
+    nr, nc, nnz = C.c_int32(0), C.c_int32(0), C.c_int64(0)
+    _ck(lib().sgm_mat_info(M._h, C.byref(nr), C.byref(nc), C.byref(nnz), None, None))
+    M.nrow, M.ncol, M.nnz = nr.value, nc.value, nnz.value
+    return M
+
+
+def sparse_matrix_sum(B, C_):
+    """A = B + C (sparse_matrix_algebra.f90:25-145), bit-identical to the reference; a new csr_matrix."""
+    return _algebra(lib().sgm_mat_sum, B, C_)
+
+
+def sparse_matrix_product(B, C_):
+    """A = B * C (sparse_matrix_algebra.f90:154-189 -> sparse_matrix_product_C :310-420); a new csr_matrix."""
+    return _algebra(lib().sgm_mat_product, B, C_)
+
+
+def PtAP(A, P):
+    """B = P^T A P (sparse_matrix_algebra.f90:425-538); a new csr_matrix."""
+    return _algebra(lib().sgm_mat_ptap, A, P)
+
+
+def RARt(A, R):
+    """B = R A R^T (sparse_matrix_algebra.f90:543-655); a new csr_matrix."""
+    return _algebra(lib().sgm_mat_rart, A, R)
 
 
 class partitioned_csr_matrix(_Matrix):

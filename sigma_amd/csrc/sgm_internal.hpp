@@ -251,6 +251,8 @@ struct Part {
 
 }  // namespace sgm
 
+namespace sgm { struct AlgPlan; void alg_plan_free(AlgPlan *p); void alg_plan_rows(const AlgPlan *p, int32_t out[2]); }   // sgm_algebra.hip
+
 struct sgm_comm_s {
     int rank = 0, nranks = 1;
     void *nccl = nullptr;          // ncclComm_t
@@ -284,6 +286,7 @@ struct sgm_mat_s {
     sgm_mat_s *T = nullptr;
     int32_t *tperm = nullptr;      // device: position in this matrix's val/eval of each entry of T
     bool t_stale = true;
+    sgm::AlgPlan *alg = nullptr;   // output of sgm_mat_sum / product / ptap / rart: its symbolic plan (sgm_algebra.hip)
 };
 
 namespace sgm {
@@ -350,6 +353,7 @@ int spmv_grid(const Part &p, bool whole = false);      // whole: the product lau
 int matvec_plain(sgm_mat A, const double *x, double *y);     // device vectors, sgm_mat_matvec's layout, stream-ordered
 // "csr_lean": the CSR-order arrays of a part that kept only its sliced form, on demand (no-op otherwise)
 int csr_need_arrays(const Part &p);
+int ensure_transpose(sgm_mat A);      // (sgm_mat.hip) A->T and A->tperm built / values refreshed; single-GPU leaves
 void csr_release_arrays(const Part &p);
 
 // sgm_trsv3.hip: slab-pipelined triangular solves for ILDU(0) factors of 3-D grids (deps r-1, r-w, r-w*h)

@@ -96,7 +96,7 @@ __global__ void k_inc1(int64_t n, int32_t *a)
     for (; i < n; i += stride) a[i] += 1;
 }
 
-static int ensure_transpose(sgm_mat A)
+int ensure_transpose(sgm_mat A)
 {
     if (A->distributed()) return fail(SGM_ERR_UNSUPPORTED, "matvec_t: not available on a row-partitioned matrix");
     Part &p = A->parts[0];
@@ -587,6 +587,9 @@ int sgm_mat_get(sgm_mat A, const char *name, void *out, size_t bytes, size_t *ne
             for (int32_t i = 0; i < p.n; ++i)
                 for (int32_t k = 0; k < p.max_d; ++k) vd[(size_t)i * p.max_d + k] = t[(size_t)k * p.n + i];
         }
+    } else if (nm == "algebra_rows" && A->alg) {      // rows the symbolic pass of sgm_mat_sum / product / ptap / rart ran on the LDS path, the long-row path
+        vi.resize(2);
+        alg_plan_rows(A->alg, vi.data());
     } else {
         return fail(SGM_ERR_BAD_ARG, "sgm_mat_get: unknown array '%s' for this format", name);
     }
@@ -720,6 +723,7 @@ int sgm_mat_destroy(sgm_mat A)
     for (auto &p : A->parts) free_part(p);
     if (A->T) sgm_mat_destroy(A->T);
     dfree(A->tperm);
+    alg_plan_free(A->alg);
     delete A;
     return SGM_OK;
 }

@@ -189,6 +189,36 @@ interface
         type(c_ptr), value :: needed
         integer(c_int) :: rc
     end function
+    ! sparse_matrix_algebra.f90:13 -- sparse_matrix_sum, sparse_matrix_product, PtAP, RARt, and the numeric refill
+    function sgm_mat_sum(out, B, C) bind(c, name='sgm_mat_sum') result(rc)
+        import :: c_ptr, c_int
+        type(c_ptr), intent(out) :: out
+        type(c_ptr), value :: B, C
+        integer(c_int) :: rc
+    end function
+    function sgm_mat_product(out, B, C) bind(c, name='sgm_mat_product') result(rc)
+        import :: c_ptr, c_int
+        type(c_ptr), intent(out) :: out
+        type(c_ptr), value :: B, C
+        integer(c_int) :: rc
+    end function
+    function sgm_mat_ptap(out, A, P) bind(c, name='sgm_mat_ptap') result(rc)
+        import :: c_ptr, c_int
+        type(c_ptr), intent(out) :: out
+        type(c_ptr), value :: A, P
+        integer(c_int) :: rc
+    end function
+    function sgm_mat_rart(out, A, R) bind(c, name='sgm_mat_rart') result(rc)
+        import :: c_ptr, c_int
+        type(c_ptr), intent(out) :: out
+        type(c_ptr), value :: A, R
+        integer(c_int) :: rc
+    end function
+    function sgm_mat_algebra_refill(out, X, Y) bind(c, name='sgm_mat_algebra_refill') result(rc)
+        import :: c_ptr, c_int
+        type(c_ptr), value :: out, X, Y
+        integer(c_int) :: rc
+    end function
     function sgm_mat_destroy(A) bind(c, name='sgm_mat_destroy') result(rc)
         import :: c_ptr, c_int
         type(c_ptr), value :: A
@@ -1372,6 +1402,74 @@ subroutine hip_csr_from_edges(A, nrow, ncol, ei, ej, ev)
     A%ncol = ncol
     if (allocated(A%ptr)) deallocate(A%ptr, A%node, A%val)
     allocate(A%ptr(nrow + 1), A%node(nnz), A%val(nnz))
+    call hip_csr_download(A)
+end subroutine
+
+
+!==========================================================================!
+!==== sparse matrix algebra (sparse_matrix_algebra.f90:13)              ====!
+!==========================================================================!
+! The result A is a new hip_csr_matrix (any handle it held is destroyed); its host arrays are read back
+! from the device.  The operands are uploaded first.
+subroutine hip_algebra_result(A, op, X, Y)
+    type(hip_csr_matrix), intent(inout), target :: A
+    integer, intent(in) :: op
+    class(hip_csr_matrix), intent(inout) :: X, Y
+    type(c_ptr) :: h
+    integer(c_int32_t) :: n32, m32, fmt
+    integer(c_int64_t) :: nnz, xl
+    call X%upload()
+    call Y%upload()
+    select case (op)
+    case (0)
+        call hip_check(sgm_mat_sum(h, X%handle, Y%handle))
+    case (1)
+        call hip_check(sgm_mat_product(h, X%handle, Y%handle))
+    case (2)
+        call hip_check(sgm_mat_ptap(h, X%handle, Y%handle))
+    case default
+        call hip_check(sgm_mat_rart(h, X%handle, Y%handle))
+    end select
+    call A%destroy()
+    A%handle = h
+    call hip_check(sgm_mat_info(A%handle, n32, m32, nnz, fmt, xl))
+    A%nrow = n32
+    A%ncol = m32
+    allocate(A%ptr(n32 + 1), A%node(nnz), A%val(nnz))
+    call hip_csr_download(A)
+end subroutine
+
+subroutine hip_sparse_matrix_sum(A, B, C)             ! A = B + C, sparse_matrix_algebra.f90:25-145
+    type(hip_csr_matrix), intent(inout), target :: A
+    class(hip_csr_matrix), intent(inout) :: B, C
+    call hip_algebra_result(A, 0, B, C)
+end subroutine
+
+subroutine hip_sparse_matrix_product(A, B, C)         ! A = B * C, :154-189 -> :310-420
+    type(hip_csr_matrix), intent(inout), target :: A
+    class(hip_csr_matrix), intent(inout) :: B, C
+    call hip_algebra_result(A, 1, B, C)
+end subroutine
+
+subroutine hip_PtAP(B, A, P)                          ! B = P^T A P, :425-538
+    type(hip_csr_matrix), intent(inout), target :: B
+    class(hip_csr_matrix), intent(inout) :: A, P
+    call hip_algebra_result(B, 2, A, P)
+end subroutine
+
+subroutine hip_RARt(B, A, R)                          ! B = R A R^T, :543-655
+    type(hip_csr_matrix), intent(inout), target :: B
+    class(hip_csr_matrix), intent(inout) :: A, R
+    call hip_algebra_result(B, 3, A, R)
+end subroutine
+
+! only the values of A again, from X / Y's current values (the operands A was built from, in the same order)
+subroutine hip_algebra_refill(A, X, Y)
+    type(hip_csr_matrix), intent(inout), target :: A
+    class(hip_csr_matrix), intent(inout) :: X, Y
+    call X%upload()
+    call Y%upload()
+    call hip_check(sgm_mat_algebra_refill(A%handle, X%handle, Y%handle))
     call hip_csr_download(A)
 end subroutine
 

@@ -325,3 +325,36 @@ def random_spd_edges(n, seed=1, p=None, skew=False):
 def test_vector(m):
     """x(i) = sin(0.001 i), 1-based i."""
     return np.sin(0.001 * np.arange(1, m + 1, dtype=F8))
+
+
+def interp2d_csr(nx, ny):
+    """2:1 linear-interpolation prolongation P from the coarse grid (the fine points of even i and j) to an nx x ny grid:
+    a fine point on a coarse point takes it with weight 1, one between two coarse points takes each with 1/2, one in the
+    middle of a coarse cell takes its four corners with 1/4 (at most 4 entries per row; an odd point on the last line of
+    an even-sized grid keeps the one neighbour it has, still with its weight).  Returns (ptr, node, val, ncoarse) with 1-based
+    ptr / node, P of shape nx*ny x ncoarse, the columns of a row ascending."""
+    cx, cy = (nx + 1) // 2, (ny + 1) // 2
+    n = nx * ny
+    k = np.arange(n, dtype=np.int64)
+    i, j = k % nx, k // nx
+
+    def along(t, c):
+        lo = t // 2
+        hi = np.where(t % 2 == 1, lo + 1, -1)
+        hi = np.where(hi >= c, -1, hi)
+        w = np.where(t % 2 == 1, 0.5, 1.0)
+        return lo, hi, w
+
+    ilo, ihi, wi = along(i, cx)
+    jlo, jhi, wj = along(j, cy)
+    cols = np.full((n, 4), -1, np.int64)
+    vals = np.zeros((n, 4))
+    for q, (jj, ii) in enumerate(((jlo, ilo), (jlo, ihi), (jhi, ilo), (jhi, ihi))):
+        ok = (jj >= 0) & (ii >= 0)
+        cols[ok, q] = jj[ok] * cx + ii[ok]
+        vals[ok, q] = wi[ok] * wj[ok]
+    keep = cols >= 0
+    cnt = keep.sum(axis=1)
+    ptr = np.zeros(n + 1, np.int64)
+    np.cumsum(cnt, out=ptr[1:])
+    return ((ptr + 1).astype(np.int32), (cols[keep] + 1).astype(np.int32), np.ascontiguousarray(vals[keep]), cx * cy)
