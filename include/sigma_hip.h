@@ -252,6 +252,50 @@ int sgm_mat_product(sgm_mat *out, sgm_mat B, sgm_mat C);   /* A = B * C   */
 int sgm_mat_ptap(sgm_mat *out, sgm_mat A, sgm_mat P);      /* B = P^T A P */
 int sgm_mat_rart(sgm_mat *out, sgm_mat A, sgm_mat R);      /* B = R A R^T */
 int sgm_mat_algebra_refill(sgm_mat out, sgm_mat X, sgm_mat Y);
+/* ---- editing values on the device (src/matrix/sparse_matrix_interfaces.f90:106-128,378-460) ------ *
+ * A batch is m triples (i_t, j_t, z_t), 1-based, processed as if the reference's scalar call were made for t = 1..m:
+ * sgm_mat_set_entries     <- A%set_value(i,j,z)   cs_matrices.f90:840-863 / ellpack_matrices.f90:444-470
+ * sgm_mat_add_entries     <- A%add_value(i,j,z)   cs_matrices.f90:868-891 / ellpack_matrices.f90:475-500; also
+ *                            set / add_multiple_values(is, js, B) (cs_matrices.f90:934-966, ellpack_matrices.f90:538-573)
+ *                            as the batch `for k: for l: (is(k), js(l), B(k,l))`, rows outer
+ * sgm_mat_get_entries     <- A%get_value(i,j)     cs_matrices.f90:709-724 / ellpack_matrices.f90:220-237: the LAST stored slot
+ *                            of row i holding j, +0.0 if there is none (never an error for an absent entry)
+ * sgm_mat_zero            <- A%zero()             val = 0.0 over every stored slot, ELLPACK padding included
+ * sgm_mat_scalar_multiply <- A%scalar_multiply(alpha)  ellpack_matrices.f90:578-596  val = alpha * val
+ * sgm_mat_add_matrix      <- A%add_sparse_matrix(B [, alpha])  sparse_matrix_interfaces.f90:430-460: B's stored entries in
+ *                            cursor order (rows ascending, stored order, ELLPACK padding skipped), z = alpha * B_ij rounded
+ *                            (alpha NULL: as they are), then added
+ * Triple t addresses EVERY stored slot k of row i_t with node(k) == j_t (a row that stores a column twice has both copies
+ * edited); an ELLPACK row is scanned over its first degrees(i) slots only, padding keeps its column and stays 0.0.  set: the z
+ * of the last triple addressing the slot.  add: ((v + z_a) + z_b) + ... in ascending t, every addition rounded on its own --
+ * the reference's bits, signed zeros / Inf / NaN included.  A triple that addresses no stored slot is SGM_ERR_UNSUPPORTED
+ * (the pattern is not grown, unlike default_sparse_matrix_kernels.f90:176-229), an index outside the matrix SGM_ERR_DIMS;
+ * the message names the smallest such t and its (i, j), and the matrix is unchanged.  `where` covers i, j and z together;
+ * m <= INT32_MAX - 4; m = 0 succeeds.  Every edit ends like sgm_csr_set_values (version bumped, kernel layouts refreshed,
+ * transpose stale; pattern_version stays).  Single-GPU CSR / ELLPACK leaves; composite, partitioned and distributed handles
+ * are SGM_ERR_UNSUPPORTED.
+ * sgm_edit_plan_create locates and orders a batch once; sgm_edit_plan_apply takes only new z (the same m values in the same
+ * order), mode SGM_EDIT_SET / SGM_EDIT_ADD, optionally after A%zero() (zero_first) -- the re-assembly of a fixed mesh as one
+ * pass over the values.  A plan belongs to its matrix: another handle, or the same one after a permutation, is
+ * SGM_ERR_BAD_ARG.  sgm_edit_plan_info: out4 = {m, slots addressed, longest chain, stored source indices incl. padding}.
+ * sgm_edit_locate_host: the locate step as host-only index work on the reference's CSR arrays (no HIP call): hit_off (m+1
+ * offsets), hit_slot (ascending 1-based positions k per triple; NULL = sizing call), needed = hit_off[m], first_missing = the
+ * smallest t without a slot or 0.                                                                                          */
+typedef struct sgm_edit_plan_s *sgm_edit_plan;
+enum { SGM_EDIT_SET = 0, SGM_EDIT_ADD = 1 };
+int sgm_mat_set_entries(sgm_mat A, int64_t m, const int32_t *i, const int32_t *j, const double *z, int where);
+int sgm_mat_add_entries(sgm_mat A, int64_t m, const int32_t *i, const int32_t *j, const double *z, int where);
+int sgm_mat_get_entries(sgm_mat A, int64_t m, const int32_t *i, const int32_t *j, double *z_out, int where);
+int sgm_mat_zero(sgm_mat A);
+int sgm_mat_scalar_multiply(sgm_mat A, double alpha);
+int sgm_mat_add_matrix(sgm_mat A, sgm_mat B, const double *alpha_or_null);
+int sgm_edit_plan_create(sgm_edit_plan *out, sgm_mat A, int64_t m, const int32_t *i, const int32_t *j, int where);
+int sgm_edit_plan_apply(sgm_edit_plan plan, sgm_mat A, const double *z, int mode, int zero_first, int where);
+int sgm_edit_plan_info(sgm_edit_plan plan, int64_t *out4);
+int sgm_edit_plan_destroy(sgm_edit_plan plan);
+int sgm_edit_locate_host(int32_t nrow, int32_t ncol, const int32_t *ptr_1based, const int32_t *node_1based, int64_t m,
+                         const int32_t *i, const int32_t *j, int64_t *hit_off, int32_t *hit_slot, int64_t capacity,
+                         int64_t *needed, int64_t *first_missing);
 /* sgm_composite_create <- type(sparse_matrix), the block "matrix of matrices"
  *                         src/matrix/sparse_matrix_composites.f90:41-162; matvec_add = loop over
  *                         the blocks `C%matvec_add(x(j1:j2), y(i1:i2))`, :1076-1099 (row blocks

@@ -9,6 +9,9 @@ hot path -- same names, argument meaning and error behaviour --
     sparse_matrix_sum(B, C), sparse_matrix_product(B, C), PtAP(A, P), RARt(A, R)
                                                sparse_matrix_algebra.f90:13; result.refill(X, Y)
     A.matvec(x, y); A.matvec_add(x, y)         linear_operator_interface.f90:185-194
+    A.set_value(i, j, z); A.add_value(i, j, z); A.get_value(i, j); A.add_multiple_values(is, js, B);
+    A.add_sparse_matrix(B, alpha); A.zero(); A.scalar_multiply(alpha)      sparse_matrix_interfaces.f90:106-128,378-460
+                                               (scalars or ordered batches, edited in HBM); edit_plan(A, i, j).add(z)
     solver = cg(tolerance)                     cg_solvers.f90:36-47
     solver = bicgstab(tolerance)               bicgstab_solvers.f90:37-48
     pc = jacobi(); pc = ldu(incomplete, level) jacobi_solvers.f90:23-31, ldu_solvers.f90:73-86
@@ -323,6 +326,78 @@ class _Matrix:
         _ck(lib().sgm_mat_get(self._h, name.encode(), C.c_void_p(out.ctypes.data), C.c_size_t(out.nbytes), None))
         return out
 
+    # -- sparse_matrix_interfaces.f90:106-128,378-460: editing the values in HBM (sgm_edit.hip) ------------
+    def _triples(self, i, j, z=None):
+        """(m, pi, pj, pz, where, keepalive): scalars or equal-length arrays = one ordered batch, all in one place"""
+        if not (_is_torch(i) or _is_torch(j) or (z is not None and _is_torch(z))):
+            i, j = np.atleast_1d(np.asarray(i, np.int32)), np.atleast_1d(np.asarray(j, np.int32))
+            if z is not None:
+                z = np.atleast_1d(np.asarray(z, np.float64))
+        m = _len(i)
+        if _len(j) != m or (z is not None and _len(z) != m):
+            raise SigmaError(2, "a batch of entries needs i, j and z of the same length")
+        pi, w1, k1 = _arg(i, np.int32)
+        pj, w2, k2 = _arg(j, np.int32)
+        if z is None:
+            return m, pi, pj, None, _same_where(w1, w2), (k1, k2)
+        pz, w3, k3 = _arg(z, np.float64)
+        return m, pi, pj, pz, _same_where(w1, w2, w3), (k1, k2, k3)
+
+    def set_value(self, i, j, z):
+        """A%set_value(i, j, z) (cs_matrices.f90:840-863, ellpack_matrices.f90:444-470) for one entry or, with arrays, for
+        t = 1..m in order: every stored slot of row i holding j gets z; the last triple wins (sgm_mat_set_entries)."""
+        m, pi, pj, pz, w, _k = self._triples(i, j, z)
+        _ck(lib().sgm_mat_set_entries(self._h, C.c_int64(m), pi, pj, pz, C.c_int(w)))
+
+    def add_value(self, i, j, z):
+        """A%add_value(i, j, z) (cs_matrices.f90:868-891) for one entry or an ordered batch: val = val + z in ascending t,
+        every addition rounded on its own (sgm_mat_add_entries).  An entry outside the pattern is refused, nothing changes."""
+        m, pi, pj, pz, w, _k = self._triples(i, j, z)
+        _ck(lib().sgm_mat_add_entries(self._h, C.c_int64(m), pi, pj, pz, C.c_int(w)))
+
+    def get_value(self, i, j):
+        """A%get_value(i, j) (cs_matrices.f90:709-724): the last stored slot of row i holding j, +0.0 if there is none; a float
+        for scalars, else an array (a device tensor when i, j are device tensors)."""
+        scalar = np.isscalar(i) and np.isscalar(j)
+        m, pi, pj, _z, w, _k = self._triples(i, j)
+        if w == SGM_DEVICE:
+            import torch
+            out = torch.zeros(m, dtype=torch.float64, device=i.device)
+        else:
+            out = np.zeros(m)
+        pz, _w, _k2 = _arg(out, np.float64, writable=True)
+        _ck(lib().sgm_mat_get_entries(self._h, C.c_int64(m), pi, pj, pz, C.c_int(w)))
+        return float(out[0]) if scalar else out
+
+    def _multiple(self, is_, js, B):
+        is_, js = np.asarray(is_, np.int32).reshape(-1), np.asarray(js, np.int32).reshape(-1)
+        B = np.asarray(B.cpu() if _is_torch(B) else B, np.float64)
+        if B.shape != (len(is_), len(js)):
+            raise SigmaError(2, f"multiple values: B is {B.shape}, is / js have {len(is_)} / {len(js)} entries")
+        return np.repeat(is_, len(js)), np.tile(js, len(is_)), np.ascontiguousarray(B).reshape(-1)      # rows outer
+
+    def set_multiple_values(self, is_, js, B):
+        """A%set_multiple_values(is, js, B): the batch for k in is: for l in js: (is(k), js(l), B(k,l))."""
+        self.set_value(*self._multiple(is_, js, B))
+
+    def add_multiple_values(self, is_, js, B):
+        """A%add_multiple_values(is, js, B) (cs_matrices.f90:934-966, ellpack_matrices.f90:538-573): rows outer."""
+        self.add_value(*self._multiple(is_, js, B))
+
+    def add_sparse_matrix(self, B, alpha=None):
+        """A%add_sparse_matrix(B [, alpha]) (sparse_matrix_interfaces.f90:430-460): B's stored entries in cursor order,
+        z = alpha * B_ij rounded, added; B's pattern must lie inside A's (sgm_mat_add_matrix)."""
+        a = None if alpha is None else C.byref(C.c_double(float(alpha)))
+        _ck(lib().sgm_mat_add_matrix(self._h, B._h, a))
+
+    def zero(self):
+        """A%zero(): every stored slot 0.0, ELLPACK padding included (sgm_mat_zero)."""
+        _ck(lib().sgm_mat_zero(self._h))
+
+    def scalar_multiply(self, alpha):
+        """A%scalar_multiply(alpha): val = alpha * val over every stored slot (sgm_mat_scalar_multiply)."""
+        _ck(lib().sgm_mat_scalar_multiply(self._h, C.c_double(float(alpha))))
+
     @classmethod
     def from_edges(cls, nrow, ncol, ei, ej, ev):
         """Assemble on the device from an edge list in insertion order (1-based), like
@@ -407,6 +482,62 @@ class csr_matrix(_Matrix):
         """(rows whose symbolic pass ran in LDS, rows that took the long-row path) of a matrix algebra result."""
         r = self.get("algebra_rows", np.int32)
         return int(r[0]), int(r[1])
+
+
+class edit_plan:
+    """sgm_edit_plan: a batch of entries (i, j) of A located and ordered once; .add(z) / .set(z) then take only new values
+    (the same m values in the same order) -- re-assembly on a fixed mesh as one pass over A's values.  The plan belongs to A:
+    another handle, or A after a permutation, is refused."""
+
+    def __init__(self, A, i, j):
+        self._h = C.c_void_p()
+        self.A = A
+        self.m, pi, pj, _z, w, _k = A._triples(i, j)
+        _ck(lib().sgm_edit_plan_create(C.byref(self._h), A._h, C.c_int64(self.m), pi, pj, C.c_int(w)))
+
+    def _apply(self, z, mode, zero_first, A=None):
+        _need(z, self.m, "edit_plan values")
+        pz, w, _k = _arg(z, np.float64)
+        _ck(lib().sgm_edit_plan_apply(self._h, (A or self.A)._h, pz, C.c_int(mode), C.c_int(1 if zero_first else 0), C.c_int(w)))
+
+    def add(self, z, zero_first=False, A=None):
+        self._apply(z, 1, zero_first, A)
+
+    def set(self, z, A=None):
+        self._apply(z, 0, False, A)
+
+    def info(self):
+        """{m, slots addressed, longest chain, stored source indices incl. padding}"""
+        out = (C.c_int64 * 4)()
+        _ck(lib().sgm_edit_plan_info(self._h, out))
+        return {"m": out[0], "slots": out[1], "longest_chain": out[2], "stored_sources": out[3]}
+
+    def destroy(self):
+        if self._h:
+            _ck(lib().sgm_edit_plan_destroy(self._h))
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def edit_locate_host(nrow, ncol, ptr, node, i, j):
+    """sgm_edit_locate_host: the locate step of the edits as host-only index work on 1-based CSR arrays; returns
+    (hit_off (m+1), hit_slot (1-based positions), first_missing (t, or 0))."""
+    ptr, node = np.ascontiguousarray(ptr, np.int32), np.ascontiguousarray(node, np.int32)
+    i, j = np.ascontiguousarray(i, np.int32), np.ascontiguousarray(j, np.int32)
+    m = len(i)
+    off = np.zeros(m + 1, np.int64)
+    needed, miss = C.c_int64(0), C.c_int64(0)
+    args = (C.c_int32(nrow), C.c_int32(ncol), C.c_void_p(ptr.ctypes.data), C.c_void_p(node.ctypes.data), C.c_int64(m),
+            C.c_void_p(i.ctypes.data), C.c_void_p(j.ctypes.data), C.c_void_p(off.ctypes.data))
+    _ck(lib().sgm_edit_locate_host(*args, None, C.c_int64(0), C.byref(needed), C.byref(miss)))
+    slot = np.zeros(needed.value, np.int32)
+    _ck(lib().sgm_edit_locate_host(*args, C.c_void_p(slot.ctypes.data), C.c_int64(len(slot)), C.byref(needed), C.byref(miss)))
+    return off, slot, miss.value
 
 
 def _algebra(fn, X, Y):

@@ -289,6 +289,27 @@ struct sgm_mat_s {
     sgm::AlgPlan *alg = nullptr;   // output of sgm_mat_sum / product / ptap / rart: its symbolic plan (sgm_algebra.hip)
 };
 
+// A located and ordered batch of value edits (sgm_edit.hip): for every ADDRESSED slot of the matrix's value array its chain of
+// source triples in ascending t, stored position-major and compacted inside groups of 64 consecutive addressed slots
+struct sgm_edit_plan_s {
+    uint64_t serial = 0, pattern_version = 0;    // the matrix the plan was made for
+    int64_t m = 0;                 // triples
+    int64_t hits = 0;              // (triple, slot) pairs
+    int64_t naddr = 0;             // addressed slots
+    int64_t nslots = 0;            // slots of the value array (nnz, or n * max_d)
+    int64_t longest = 0;           // longest chain
+    int64_t padded = 0;            // 4-byte words of the groups' records: sources, masks, widths
+    int64_t long_entries = 0;      // sources of the long-chain list
+    int32_t nlong = 0;             // chains kept out of the groups
+    int32_t *uslot = nullptr;      // naddr: the slot, ascending
+    int32_t *ulast = nullptr;      // naddr: its last source (what `set` writes)
+    int64_t *goff = nullptr;       // groups + 1: where a group's record starts in gsrc
+    int32_t *gsrc = nullptr;       // group record: W, W 64-bit lane masks (lo, hi), then per position the sources of the masked lanes
+    int32_t *lg = nullptr;         // nlong: addressed-slot numbers of the long chains
+    int32_t *ustart = nullptr;     // naddr + 1: chain starts in hsrc (kept with the long list only)
+    int32_t *hsrc = nullptr;       // sources sorted by slot, stable (kept with the long list only)
+};
+
 namespace sgm {
 
 // y = [y +] A^T x on a matrix distributed over processes (sgm_dist.hip): x = owned rows, y = owned columns

@@ -267,6 +267,61 @@ inline int host_left_permute_rows_host(int32_t n, const int32_t *p, const int32_
     return SGM_OK;
 }
 
+// ------------------------------------------------------------------ locate step of the value edits (sgm_edit.hip)
+// A batch of triples (i_t, j_t, z_t) edits every stored slot k of row i_t with node(k) == j_t (the reference's set_value /
+// add_value loops do not stop at the first match: cs_matrices.f90:840-891, ellpack_matrices.f90:444-500).  The row scan is ONE
+// function for the host planner below and for the device kernels: SGM_HD is __host__ __device__ under hipcc and empty under a
+// plain C++ compiler (tools/asan).  Slots lo, lo + stride, ... (hi exclusive, counted in steps) are compared with `key`; every
+// match is handed to f(step).  Returns the number of matches.
+#if defined(__HIPCC__)
+#define SGM_HD __host__ __device__
+#else
+#define SGM_HD
+#endif
+template <class F>
+SGM_HD inline int32_t edit_scan_row(const int32_t *node, int64_t first, int64_t stride, int32_t steps, int32_t key, F &&f)
+{
+    int32_t hits = 0;
+    for (int32_t u = 0; u < steps; ++u)
+        if (node[first + (int64_t)u * stride] == key) { f(u); ++hits; }
+    return hits;
+}
+
+// CSR arrays as the reference holds them (1-based ptr / node; rows may be unsorted and may store a column twice).
+// hit_off[t] .. hit_off[t+1]: the hits of triple t+1 in hit_slot, ascending 1-based positions k of node / val.
+// first_missing: the smallest 1-based t that addresses no slot (0: none).  needed = hit_off[m]; hit_slot may be null
+// (sizing call).  An index outside 1..nrow / 1..ncol is SGM_ERR_DIMS naming the smallest such t.
+inline int host_edit_locate_host(int32_t nrow, int32_t ncol, const int32_t *ptr, const int32_t *node, int64_t m, const int32_t *i,
+                                 const int32_t *j, int64_t *hit_off, int32_t *hit_slot, int64_t capacity, int64_t *needed,
+                                 int64_t *first_missing)
+{
+    if (nrow < 0 || ncol < 0 || !ptr || m < 0 || (m && (!i || !j)) || !hit_off)
+        return fail(SGM_ERR_BAD_ARG, "sgm_edit_locate_host: bad argument");
+    for (int64_t t = 0; t < m; ++t)
+        if (i[t] < 1 || i[t] > nrow || j[t] < 1 || j[t] > ncol)
+            return fail(SGM_ERR_DIMS, "sgm_edit_locate_host: triple %lld addresses (%d, %d) outside %d x %d", (long long)t + 1, i[t], j[t], nrow, ncol);
+    int64_t total = 0, miss = 0;
+    hit_off[0] = 0;
+    for (int64_t t = 0; t < m; ++t) {
+        const int64_t lo = (int64_t)ptr[i[t] - 1] - 1;
+        const int32_t len = ptr[i[t]] - ptr[i[t] - 1];
+        const int32_t c = edit_scan_row(node, lo, 1, len, j[t], [](int32_t) {});
+        if (c == 0 && miss == 0) miss = t + 1;
+        total += c;
+        hit_off[t + 1] = total;
+    }
+    if (needed) *needed = total;
+    if (first_missing) *first_missing = miss;
+    if (!hit_slot) return SGM_OK;                    // sizing call
+    if (capacity < total) return fail(SGM_ERR_BAD_ARG, "sgm_edit_locate_host: %lld hits do not fit %lld", (long long)total, (long long)capacity);
+    for (int64_t t = 0; t < m; ++t) {
+        const int64_t lo = (int64_t)ptr[i[t] - 1] - 1;
+        int64_t w = hit_off[t];
+        edit_scan_row(node, lo, 1, ptr[i[t]] - ptr[i[t] - 1], j[t], [&](int32_t u) { hit_slot[w++] = (int32_t)(lo + u) + 1; });
+    }
+    return SGM_OK;
+}
+
 // ---- slice schedule ---------------------------------------------------------------------------------
 // A 3-D grid's rows reference x a whole plane away (offset +-D, D >> one slice).  With slices handed out round-robin or
 // block-cyclic, the slices D rows apart -- which read the same x lines -- run on different XCDs, so every x line enters

@@ -219,6 +219,89 @@ interface
         type(c_ptr), value :: out, X, Y
         integer(c_int) :: rc
     end function
+    ! ---- editing values on the device (sgm_edit.hip): ordered set / add batches and plans
+    function sgm_mat_set_entries(A, m, i, j, z, where) bind(c, name='sgm_mat_set_entries') result(rc)
+        import :: c_int, c_ptr, c_int32_t, c_int64_t, c_double
+        type(c_ptr), value :: A
+        integer(c_int64_t), value :: m
+        integer(c_int32_t), intent(in) :: i(*), j(*)
+        real(c_double), intent(in) :: z(*)
+        integer(c_int), value :: where
+        integer(c_int) :: rc
+    end function
+    function sgm_mat_add_entries(A, m, i, j, z, where) bind(c, name='sgm_mat_add_entries') result(rc)
+        import :: c_int, c_ptr, c_int32_t, c_int64_t, c_double
+        type(c_ptr), value :: A
+        integer(c_int64_t), value :: m
+        integer(c_int32_t), intent(in) :: i(*), j(*)
+        real(c_double), intent(in) :: z(*)
+        integer(c_int), value :: where
+        integer(c_int) :: rc
+    end function
+    function sgm_mat_get_entries(A, m, i, j, z, where) bind(c, name='sgm_mat_get_entries') result(rc)
+        import :: c_int, c_ptr, c_int32_t, c_int64_t, c_double
+        type(c_ptr), value :: A
+        integer(c_int64_t), value :: m
+        integer(c_int32_t), intent(in) :: i(*), j(*)
+        real(c_double), intent(inout) :: z(*)
+        integer(c_int), value :: where
+        integer(c_int) :: rc
+    end function
+    function sgm_mat_zero(A) bind(c, name='sgm_mat_zero') result(rc)
+        import :: c_int, c_ptr
+        type(c_ptr), value :: A
+        integer(c_int) :: rc
+    end function
+    function sgm_mat_scalar_multiply(A, alpha) bind(c, name='sgm_mat_scalar_multiply') result(rc)
+        import :: c_int, c_ptr, c_double
+        type(c_ptr), value :: A
+        real(c_double), value :: alpha
+        integer(c_int) :: rc
+    end function
+    function sgm_mat_add_matrix(A, B, alpha) bind(c, name='sgm_mat_add_matrix') result(rc)
+        import :: c_int, c_ptr
+        type(c_ptr), value :: A, B
+        type(c_ptr), value :: alpha          ! c_loc of a real(c_double), or c_null_ptr
+        integer(c_int) :: rc
+    end function
+    function sgm_edit_plan_create(plan, A, m, i, j, where) bind(c, name='sgm_edit_plan_create') result(rc)
+        import :: c_int, c_ptr, c_int32_t, c_int64_t
+        type(c_ptr), intent(out) :: plan
+        type(c_ptr), value :: A
+        integer(c_int64_t), value :: m
+        integer(c_int32_t), intent(in) :: i(*), j(*)
+        integer(c_int), value :: where
+        integer(c_int) :: rc
+    end function
+    function sgm_edit_plan_apply(plan, A, z, mode, zero_first, where) bind(c, name='sgm_edit_plan_apply') result(rc)
+        import :: c_int, c_ptr, c_double
+        type(c_ptr), value :: plan, A
+        real(c_double), intent(in) :: z(*)
+        integer(c_int), value :: mode, zero_first, where
+        integer(c_int) :: rc
+    end function
+    function sgm_edit_plan_info(plan, out4) bind(c, name='sgm_edit_plan_info') result(rc)
+        import :: c_int, c_ptr, c_int64_t
+        type(c_ptr), value :: plan
+        integer(c_int64_t), intent(out) :: out4(4)
+        integer(c_int) :: rc
+    end function
+    function sgm_edit_plan_destroy(plan) bind(c, name='sgm_edit_plan_destroy') result(rc)
+        import :: c_int, c_ptr
+        type(c_ptr), value :: plan
+        integer(c_int) :: rc
+    end function
+    function sgm_edit_locate_host(nrow, ncol, ptr, node, m, i, j, hit_off, hit_slot, capacity, needed, first_missing) &
+            & bind(c, name='sgm_edit_locate_host') result(rc)
+        import :: c_int, c_ptr, c_int32_t, c_int64_t
+        integer(c_int32_t), value :: nrow, ncol
+        integer(c_int32_t), intent(in) :: ptr(*), node(*), i(*), j(*)
+        integer(c_int64_t), value :: m, capacity
+        integer(c_int64_t), intent(out) :: hit_off(*)
+        type(c_ptr), value :: hit_slot       ! c_loc of capacity int32, or c_null_ptr (sizing call)
+        integer(c_int64_t), intent(out) :: needed, first_missing
+        integer(c_int) :: rc
+    end function
     function sgm_mat_destroy(A) bind(c, name='sgm_mat_destroy') result(rc)
         import :: c_ptr, c_int
         type(c_ptr), value :: A
@@ -657,6 +740,10 @@ contains
     procedure :: upload => hip_csr_upload
     procedure :: left_permute => hip_csr_left_permute
     procedure :: right_permute => hip_csr_right_permute
+    procedure :: set_values_at => hip_csr_set_values_at
+    procedure :: add_values_at => hip_csr_add_values_at
+    procedure :: add_multiple_values => hip_csr_add_multiple_values
+    procedure :: scalar_multiply => hip_csr_scalar_multiply
     procedure :: destroy => hip_csr_destroy
 end type hip_csr_matrix
 
@@ -678,6 +765,10 @@ contains
     procedure :: set_value => hip_ell_set_value
     procedure :: zero => hip_ell_zero
     procedure :: upload => hip_ell_upload
+    procedure :: set_values_at => hip_ell_set_values_at
+    procedure :: add_values_at => hip_ell_add_values_at
+    procedure :: add_multiple_values => hip_ell_add_multiple_values
+    procedure :: scalar_multiply => hip_ell_scalar_multiply
     procedure :: destroy => hip_ell_destroy
 end type hip_ellpack_matrix
 
@@ -996,6 +1087,105 @@ subroutine hip_csr_download(A)
     call hip_check(sgm_mat_get(A%handle, 'val'//c_null_char, c_loc(A%val), &
         & int(8 * size(A%val), c_size_t), c_null_ptr))
     A%values_dirty = .false.
+end subroutine
+
+! Batches of edits on the device (sgm_edit.hip): the triples (is(t), js(t), zs(t)) as if set_value / add_value were called for
+! t = 1, 2, ...; the matrix is uploaded, edited in HBM and the host copy of val refreshed, like the permutations above.  An
+! entry outside the pattern ends the program (hip_check), as the scalar set_value does.
+subroutine hip_csr_set_values_at(A, is, js, zs)        ! cs_matrices.f90:840-863, one call per triple
+    class(hip_csr_matrix), intent(inout), target :: A
+    integer, intent(in) :: is(:), js(:)
+    real(dp), intent(in) :: zs(:)
+    call A%upload()
+    call hip_check(sgm_mat_set_entries(A%handle, int(size(is), c_int64_t), int(is, c_int32_t), int(js, c_int32_t), zs, SGM_HOST))
+    call hip_edit_download(A%handle, c_loc(A%val), size(A%val))
+end subroutine
+
+subroutine hip_csr_add_values_at(A, is, js, zs)        ! cs_matrices.f90:868-891
+    class(hip_csr_matrix), intent(inout), target :: A
+    integer, intent(in) :: is(:), js(:)
+    real(dp), intent(in) :: zs(:)
+    call A%upload()
+    call hip_check(sgm_mat_add_entries(A%handle, int(size(is), c_int64_t), int(is, c_int32_t), int(js, c_int32_t), zs, SGM_HOST))
+    call hip_edit_download(A%handle, c_loc(A%val), size(A%val))
+end subroutine
+
+subroutine hip_csr_add_multiple_values(A, is, js, B)   ! cs_matrices.f90:934-966: rows outer
+    class(hip_csr_matrix), intent(inout), target :: A
+    integer, intent(in) :: is(:), js(:)
+    real(dp), intent(in) :: B(:,:)
+    integer, allocatable :: ti(:), tj(:)
+    real(dp), allocatable :: tz(:)
+    call hip_edit_expand(is, js, B, ti, tj, tz)
+    call hip_csr_add_values_at(A, ti, tj, tz)
+end subroutine
+
+subroutine hip_csr_scalar_multiply(A, alpha)
+    class(hip_csr_matrix), intent(inout), target :: A
+    real(dp), intent(in) :: alpha
+    call A%upload()
+    call hip_check(sgm_mat_scalar_multiply(A%handle, alpha))
+    call hip_edit_download(A%handle, c_loc(A%val), size(A%val))
+end subroutine
+
+subroutine hip_ell_set_values_at(A, is, js, zs)        ! ellpack_matrices.f90:444-470
+    class(hip_ellpack_matrix), intent(inout), target :: A
+    integer, intent(in) :: is(:), js(:)
+    real(dp), intent(in) :: zs(:)
+    call A%upload()
+    call hip_check(sgm_mat_set_entries(A%handle, int(size(is), c_int64_t), int(is, c_int32_t), int(js, c_int32_t), zs, SGM_HOST))
+    call hip_edit_download(A%handle, c_loc(A%val), size(A%val))
+end subroutine
+
+subroutine hip_ell_add_values_at(A, is, js, zs)        ! ellpack_matrices.f90:475-500
+    class(hip_ellpack_matrix), intent(inout), target :: A
+    integer, intent(in) :: is(:), js(:)
+    real(dp), intent(in) :: zs(:)
+    call A%upload()
+    call hip_check(sgm_mat_add_entries(A%handle, int(size(is), c_int64_t), int(is, c_int32_t), int(js, c_int32_t), zs, SGM_HOST))
+    call hip_edit_download(A%handle, c_loc(A%val), size(A%val))
+end subroutine
+
+subroutine hip_ell_add_multiple_values(A, is, js, B)   ! ellpack_matrices.f90:538-573: rows outer
+    class(hip_ellpack_matrix), intent(inout), target :: A
+    integer, intent(in) :: is(:), js(:)
+    real(dp), intent(in) :: B(:,:)
+    integer, allocatable :: ti(:), tj(:)
+    real(dp), allocatable :: tz(:)
+    call hip_edit_expand(is, js, B, ti, tj, tz)
+    call hip_ell_add_values_at(A, ti, tj, tz)
+end subroutine
+
+subroutine hip_ell_scalar_multiply(A, alpha)           ! ellpack_matrices.f90:578-596
+    class(hip_ellpack_matrix), intent(inout), target :: A
+    real(dp), intent(in) :: alpha
+    call A%upload()
+    call hip_check(sgm_mat_scalar_multiply(A%handle, alpha))
+    call hip_edit_download(A%handle, c_loc(A%val), size(A%val))
+end subroutine
+
+subroutine hip_edit_expand(is, js, B, ti, tj, tz)
+    integer, intent(in) :: is(:), js(:)
+    real(dp), intent(in) :: B(:,:)
+    integer, allocatable, intent(out) :: ti(:), tj(:)
+    real(dp), allocatable, intent(out) :: tz(:)
+    integer :: k, l, t
+    allocate(ti(size(is) * size(js)), tj(size(is) * size(js)), tz(size(is) * size(js)))
+    t = 0
+    do k = 1, size(is)
+        do l = 1, size(js)
+            t = t + 1
+            ti(t) = is(k)
+            tj(t) = js(l)
+            tz(t) = B(k, l)
+        enddo
+    enddo
+end subroutine
+
+subroutine hip_edit_download(handle, val, count)
+    type(c_ptr), intent(in) :: handle, val
+    integer, intent(in) :: count
+    call hip_check(sgm_mat_get(handle, 'val'//c_null_char, val, int(8 * count, c_size_t), c_null_ptr))
 end subroutine
 
 ! src/graph/permutations.f90 on the matrix graph (the routines take the matrix, which owns it)

@@ -61,6 +61,11 @@ int sgm_left_permute_rows_host(int32_t n, const int32_t *p, const int32_t *ptr, 
 {
     return host_left_permute_rows_host(n, p, ptr, node, val, r0, r1, lptr, lnode, lval, capacity, needed);
 }
+int sgm_edit_locate_host(int32_t nrow, int32_t ncol, const int32_t *ptr, const int32_t *node, int64_t m, const int32_t *i, const int32_t *j,
+                         int64_t *hit_off, int32_t *hit_slot, int64_t capacity, int64_t *needed, int64_t *first_missing)
+{
+    return host_edit_locate_host(nrow, ncol, ptr, node, m, i, j, hit_off, hit_slot, capacity, needed, first_missing);
+}
 int sgm_slice_sched_host(int64_t n_slices, int64_t period_rows, int32_t grid, int32_t band_slices, int32_t *tab_out,
                          int64_t capacity, int32_t *iters_out)
 {
