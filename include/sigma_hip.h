@@ -50,6 +50,7 @@ enum { SGM_HOST = 0, SGM_DEVICE = 1 };
 enum { SGM_FMT_CSR = 1, SGM_FMT_ELL = 2, SGM_FMT_COMPOSITE = 3 };
 enum { SGM_SOLVER_CG = 1, SGM_SOLVER_BICGSTAB = 2, SGM_SOLVER_GMRES = 3 };
 enum { SGM_PC_JACOBI = 1, SGM_PC_ILDU0 = 2 };
+#define SGM_PC_MG 3        /* multigrid V-cycle: made by sgm_mg_create (it needs its prolongations), not by sgm_pc_create */
 
 /* ---- runtime -------------------------------------------------------------------- */
 int sgm_init(int device);                 /* hipSetDevice + stream; fails loudly without a GPU */
@@ -390,6 +391,31 @@ int sgm_pc_get(sgm_pc pc, const char *name, void *out_host, size_t bytes, size_t
  * (option "ildu_reorder"), INTEGRATION.md. */
 int sgm_pc_info(sgm_pc pc, int32_t part, int32_t *out4, double *est_us, char *path_name, int len);
 int sgm_pc_destroy(sgm_pc pc);
+
+/* ---- multigrid preconditioner (an extension: the reference has PtAP / RARt "for multigrid setup" and no multigrid) ---- *
+ * sgm_mg_create: one V-cycle on Galerkin levels with damped Jacobi sweeps.  P[l] (l = 0 .. ncoarse-1, borrowed: they must
+ * outlive the preconditioner) is the n_l x n_{l+1} CSR prolongation of level l; ncoarse = 0 is the coarse sweeps on A alone.
+ * sgm_pc_setup(pc, A) builds A_{l+1} = P_l^T A_l P_l with sgm_mat_ptap (owned by the preconditioner), the inverse diagonals
+ * (the Jacobi setup's rule) and the work vectors; a second setup with the same handles and unchanged patterns refills the
+ * levels through sgm_mat_algebra_refill, anything else rebuilds them.  z = M^-1 r is vcycle(0, r), every operation rounded
+ * on its own, row sums as sgm_mat_matvec forms them:
+ *   first sweep of a level (zero start)   x(i) = omega * (idiag(i) * b(i))
+ *   further sweeps, out of place          q = A_l x ; t(i) = b(i) - q(i) ; x'(i) = x(i) + omega * (idiag(i) * t(i))
+ *   coarsest level                        coarse_sweeps sweeps
+ *   other levels                          nu_pre sweeps ; r = b - A_l x ; b_c = sgm_mat_matvec_t(P_l, r) ; x_c = vcycle(l+1, b_c) ;
+ *                                         sgm_mat_matvec_add(P_l, x_c, x) ; nu_post sweeps
+ * nu_pre >= 1, nu_post >= 0, coarse_sweeps >= 1 (SGM_ERR_BAD_ARG otherwise).  With nu_pre == nu_post, A symmetric positive
+ * definite and 0 < omega * lambda_max(D^-1 A) < 2 the operator is symmetric positive definite (usable inside CG); the
+ * library does not check this.  Setup refuses with SGM_ERR_DIMS when A is not square or the row counts of the P_l do not
+ * chain, with SGM_ERR_UNSUPPORTED (naming the level) for ELLPACK, composite, partitioned or distributed A or P; after a
+ * refused setup the handle can only be set up again or destroyed.
+ * sgm_pc_info: out4 = {levels, levels, 5, 0}, path_name e.g. "V(1,1) omega 0.8, 7 levels, 8 coarse sweeps".
+ * sgm_pc_get: "mg_paths" (int32 per level: 1 = sweeps fused on the 4-bit sliced form, 2 = fused on the 1-byte sliced form (rows of up to 9 or 27 entries),
+ * 0 = product + elementwise pass), "mg_idiag_<l>" (the inverse diagonal of level l).
+ * sgm_mg_level_matrix: A_level after setup (level 0 = the caller's A), borrowed: do not destroy it.                        */
+int sgm_mg_create(sgm_pc *out, int32_t ncoarse, const sgm_mat *P /* ncoarse handles, borrowed */,
+                  double omega, int32_t nu_pre, int32_t nu_post, int32_t coarse_sweeps);
+int sgm_mg_level_matrix(sgm_pc pc, int32_t level, sgm_mat *borrowed);   /* A_level after setup; level 0 = the caller's A */
 
 /* ---- solvers ------------------------------------------------------------------------ *
  * sgm_cg_create       <- cg(tolerance)            src/solver/cg_solvers.f90:36-47

@@ -15,6 +15,7 @@ hot path -- same names, argument meaning and error behaviour --
     solver = cg(tolerance)                     cg_solvers.f90:36-47
     solver = bicgstab(tolerance)               bicgstab_solvers.f90:37-48
     pc = jacobi(); pc = ldu(incomplete, level) jacobi_solvers.f90:23-31, ldu_solvers.f90:73-86
+    pc = multigrid(P, omega, nu_pre, nu_post)  V-cycle on the Galerkin levels of the prolongations P (an extension)
     solver.setup(A); pc.setup(A)
     solver.solve(A, x, b[, pc])                generic solve: linear_solve / linear_solve_pc
     solver.iterations, solver.tolerance, solver.nn, solver.initialized
@@ -808,6 +809,60 @@ class sparse_ldu_solver(_Preconditioner):
 def jacobi():
     """jacobi() factory (jacobi_solvers.f90:23-31)."""
     return jacobi_solver()
+
+
+class _LevelMatrix(csr_matrix):
+    """A level matrix of a multigrid preconditioner: a csr_matrix handle the preconditioner owns (destroy is a no-op)."""
+
+    def destroy(self):
+        self._h = C.c_void_p()
+
+
+class multigrid_solver(_Preconditioner):
+    """One V-cycle on Galerkin levels with damped Jacobi sweeps (sgm_mg_create; include/sigma_hip.h states the contract)."""
+    _kind = 3       # SGM_PC_MG
+
+    def __init__(self, P, omega, nu_pre, nu_post, coarse_sweeps):
+        super().__init__()
+        self.P = list(P)            # borrowed by the library: kept alive here
+        hs = (C.c_void_p * max(len(self.P), 1))(*[p._h for p in self.P])
+        _ck(lib().sgm_mg_create(C.byref(self._h), C.c_int32(len(self.P)), hs, C.c_double(float(omega)),
+                                C.c_int32(int(nu_pre)), C.c_int32(int(nu_post)), C.c_int32(int(coarse_sweeps))))
+
+    @property
+    def levels(self):
+        return len(self.P) + 1
+
+    def level_handle(self, level):
+        """A_level as a matrix object (level 0 = the caller's A); it belongs to the preconditioner."""
+        M = _LevelMatrix.__new__(_LevelMatrix)
+        _Matrix.__init__(M)
+        _ck(lib().sgm_mg_level_matrix(self._h, C.c_int32(int(level)), C.byref(M._h)))
+        nr, nc, nnz = C.c_int32(0), C.c_int32(0), C.c_int64(0)
+        _ck(lib().sgm_mat_info(M._h, C.byref(nr), C.byref(nc), C.byref(nnz), None, None))
+        M.nrow, M.ncol, M.nnz = nr.value, nc.value, nnz.value
+        return M
+
+    def level_matrix(self, level):
+        """(nrow, ncol, ptr, node, val) of A_level, 1-based like the reference."""
+        M = self.level_handle(level)
+        return M.nrow, M.ncol, M.get("ptr", np.int32), M.get("node", np.int32), M.get("val", np.float64)
+
+    def paths(self):
+        """per level: 1 = sweeps fused on the 4-bit sliced form, 2 = on the 1-byte sliced form, 0 = product + elementwise pass"""
+        return self.get("mg_paths", np.int32)
+
+    def idiag(self, level):
+        return self.get(f"mg_idiag_{int(level)}", np.float64)
+
+
+def multigrid(P, omega=2.0 / 3.0, nu_pre=1, nu_post=1, coarse_sweeps=8):
+    """V(nu_pre, nu_post) multigrid preconditioner on the Galerkin hierarchy of the prolongations P (a list of csr_matrix,
+    P[l] of shape n_l x n_{l+1}; an empty list = the coarse sweeps on A alone): damped Jacobi sweeps with weight omega,
+    coarse_sweeps of them on the last level.  An extension: the reference has PtAP "for multigrid setup" and no multigrid.
+    Symmetric positive definite -- valid inside cg -- when nu_pre == nu_post, A is SPD and 0 < omega * lambda_max(D^-1 A) < 2
+    (not checked)."""
+    return multigrid_solver(P, omega, nu_pre, nu_post, coarse_sweeps)
 
 
 def ldu(incomplete=True, level=0, reorder=None):

@@ -253,6 +253,20 @@ struct Part {
 
 namespace sgm { struct AlgPlan; void alg_plan_free(AlgPlan *p); void alg_plan_rows(const AlgPlan *p, int32_t out[2]); }   // sgm_algebra.hip
 
+// sgm_mg.hip: the state of a multigrid preconditioner (SGM_PC_MG), opaque to the pc functions of sgm_pc.hip, and the hooks they
+// call; pc_adopt_mg / pc_mg (sgm_pc.hip) wrap a state in a handle and give it back
+namespace sgm {
+struct MgState;
+int mg_setup(MgState *S, sgm_mat A);
+int mg_apply(MgState *S, const double *r, double *z, const int *flag);      // device vectors, stream-ordered
+int mg_apply_vectors(MgState *S, const double *r, double *z, int where);    // sgm_pc_apply: host or device vectors
+int mg_get(MgState *S, const char *name, const void **src, size_t *sz);     // "mg_paths", "mg_idiag_<l>"
+int mg_info(MgState *S, int32_t out4[4], double *est_us, char *name, size_t len);
+void mg_free(MgState *S);
+sgm_pc pc_adopt_mg(MgState *S);
+MgState *pc_mg(sgm_pc pc);         // null: not a multigrid preconditioner
+}
+
 struct sgm_comm_s {
     int rank = 0, nranks = 1;
     void *nccl = nullptr;          // ncclComm_t

@@ -200,6 +200,7 @@ struct sgm_pc_s {
     sgm_mat Ap = nullptr;
     uint64_t Ap_serial = 0, Ap_version = 0;            // ... of the matrix it is the permutation of
     bool in_permuted = false;
+    sgm::MgState *mg = nullptr;        // SGM_PC_MG: the hierarchy and its work vectors (sgm_mg.hip)
 };
 
 namespace {
@@ -2490,11 +2491,20 @@ int ensure_host_pattern(IlduState *S)
 namespace sgm {
 
 int pc_kind(sgm_pc pc) { return pc ? pc->kind : 0; }
+sgm_pc pc_adopt_mg(MgState *S)
+{
+    sgm_pc pc = new sgm_pc_s;
+    pc->kind = SGM_PC_MG;
+    pc->mg = S;
+    return pc;
+}
+MgState *pc_mg(sgm_pc pc) { return pc && pc->kind == SGM_PC_MG ? pc->mg : nullptr; }
 // an apply that is a handful of launches (Jacobi; ILDU through the strip / slab pipeline or over a few wide levels) lets the
 // solvers queue a whole batch of iterations between two looks at the stop flag; thousands of level launches per apply do not
 bool pc_apply_is_short(sgm_pc pc)
 {
     if (!pc || pc->kind == SGM_PC_JACOBI) return true;
+    if (pc->kind == SGM_PC_MG) return false;      // a V-cycle is tens of launches: the solvers look at the stop flag after each iteration
     // (a colour-ordered matrix has two or three levels per factor: its level-scheduled apply is seven to nine launches)
     for (const auto &S : pc->ild) {
         if (pc->opt.ildu_strips && (S.grid_ok || S.slab_ok)) continue;
@@ -2626,6 +2636,10 @@ int pc_apply_parts(sgm_pc pc, sgm_mat A, const double *const *r, double *const *
 static int pc_apply_parts_ordered(sgm_pc pc, sgm_mat A, const double *const *r, double *const *z, const int *const *flags)
 {
     hipStream_t st = g_rt.stream;
+    if (pc->kind == SGM_PC_MG) {
+        if (A->parts.size() != 1) return fail(SGM_ERR_UNSUPPORTED, "multigrid: single-GPU matrices only");
+        return mg_apply(pc->mg, r[0], z[0], flags ? flags[0] : nullptr);
+    }
     if (pc->kind == SGM_PC_JACOBI) {
         for (size_t ip = 0; ip < A->parts.size(); ++ip) {
             const int64_t n = A->parts[ip].n;
@@ -2686,6 +2700,11 @@ int sgm_pc_setup(sgm_pc pc, sgm_mat A)
 {
     SGM_TRY(require_init());
     if (!pc || !A) return fail(SGM_ERR_BAD_ARG, "sgm_pc_setup: null argument");
+    if (pc->kind == SGM_PC_MG) {
+        SGM_TRY(mg_setup(pc->mg, A));
+        pc->n = A->nrow;
+        return SGM_OK;
+    }
     const bool reorder = pc->kind == SGM_PC_ILDU0 && pc->opt.ildu_reorder && A->fmt == SGM_FMT_CSR && A->nrow == A->ncol && A->nrow > 0;
     if (!reorder) {
         if (!pc->ro.empty()) { free_reorder(pc); for (auto &S : pc->ild) free_ildu(S); pc->ild.clear(); }
@@ -3099,7 +3118,8 @@ static int pc_setup_ordered(sgm_pc pc, sgm_mat A)
  * that has seen no matrix yet; options can be set on it before the first sgm_pc_setup builds its sweeps. */
 int sgm_pc_create(sgm_pc *out, int32_t kind)
 {
-    if (!out || (kind != SGM_PC_JACOBI && kind != SGM_PC_ILDU0)) return fail(SGM_ERR_BAD_ARG, "sgm_pc_create: kind is SGM_PC_JACOBI or SGM_PC_ILDU0");
+    if (!out || (kind != SGM_PC_JACOBI && kind != SGM_PC_ILDU0))      // (SGM_PC_MG needs its prolongations: sgm_mg_create)
+        return fail(SGM_ERR_BAD_ARG, "sgm_pc_create: kind is SGM_PC_JACOBI or SGM_PC_ILDU0");
     sgm_pc pc = new sgm_pc_s;
     pc->kind = kind;
     *out = pc;
@@ -3147,6 +3167,7 @@ int sgm_pc_apply(sgm_pc pc, const double *r, double *z, int where)
 {
     SGM_TRY(require_init());
     if (!pc || !r || !z) return fail(SGM_ERR_BAD_ARG, "sgm_pc_apply: null argument");
+    if (pc->kind == SGM_PC_MG) return mg_apply_vectors(pc->mg, r, z, where);
     if (pc->kind == SGM_PC_JACOBI && pc->parts.size() != 1)
         return fail(SGM_ERR_UNSUPPORTED, "sgm_pc_apply: stand-alone apply needs a single-part matrix");
     // the vectors hold THIS process's rows: all of them on one GPU or an in-process partition, this rank's block when the
@@ -3201,6 +3222,15 @@ int sgm_pc_get(sgm_pc pc, const char *name, void *out, size_t bytes, size_t *nee
     size_t sz = 0;
     std::string nm(name);
     static const char kEmpty = 0;
+    if (pc->kind == SGM_PC_MG) {
+        SGM_TRY(mg_get(pc->mg, name, &src, &sz));
+        if (needed) *needed = sz;
+        if (out && sz) {
+            if (bytes < sz) return fail(SGM_ERR_BAD_ARG, "sgm_pc_get: buffer too small (%zu < %zu)", bytes, sz);
+            memcpy(out, src, sz);
+        }
+        return SGM_OK;
+    }
     if (pc->kind == SGM_PC_JACOBI && nm == "idiag") {
         if (pc->parts.size() != 1) return fail(SGM_ERR_UNSUPPORTED, "sgm_pc_get(idiag): single-part only");
         pc->hidiag.resize((size_t)pc->n);
@@ -3304,6 +3334,10 @@ int sgm_pc_get(sgm_pc pc, const char *name, void *out, size_t bytes, size_t *nee
 int sgm_pc_info(sgm_pc pc, int32_t part, int32_t *out4, double *est_us, char *path_name, int len)
 {
     if (!pc) return fail(SGM_ERR_BAD_ARG, "sgm_pc_info: null preconditioner");
+    if (pc->kind == SGM_PC_MG) {
+        if (part != 0) return fail(SGM_ERR_BAD_ARG, "sgm_pc_info: part %d", part);
+        return mg_info(pc->mg, out4, est_us, path_name, len > 0 ? (size_t)len : 0);
+    }
     int32_t o[4] = {1, 1, 0, 0};
     double us = 0.0;
     char nm[160] = "";
@@ -3371,6 +3405,7 @@ int sgm_pc_destroy(sgm_pc pc)
     dfree(pc->abort_sticky);
     free_reorder(pc);
     if (pc->Ap) sgm_mat_destroy(pc->Ap);
+    mg_free(pc->mg);
     delete pc;
     return SGM_OK;
 }

@@ -686,6 +686,22 @@ interface
         integer(c_int32_t), value :: kind          ! 1 jacobi, 2 ildu(0)
         integer(c_int) :: rc
     end function
+    function sgm_mg_create(pc, ncoarse, P, omega, nu_pre, nu_post, coarse_sweeps) bind(c, name='sgm_mg_create') result(rc)
+        import :: c_ptr, c_int, c_int32_t, c_double
+        type(c_ptr), intent(out) :: pc
+        integer(c_int32_t), value :: ncoarse
+        type(c_ptr), intent(in) :: P(*)            ! ncoarse matrix handles, borrowed
+        real(c_double), value :: omega
+        integer(c_int32_t), value :: nu_pre, nu_post, coarse_sweeps
+        integer(c_int) :: rc
+    end function
+    function sgm_mg_level_matrix(pc, level, borrowed) bind(c, name='sgm_mg_level_matrix') result(rc)
+        import :: c_ptr, c_int, c_int32_t
+        type(c_ptr), value :: pc
+        integer(c_int32_t), value :: level
+        type(c_ptr), intent(out) :: borrowed       ! A_level after setup (level 0 = the caller's A); not to be destroyed
+        integer(c_int) :: rc
+    end function
     function c_usleep(us) bind(c, name='usleep') result(rc)
         import :: c_int
         integer(c_int), value :: us
@@ -1332,6 +1348,48 @@ function hip_jacobi() result(s)                    ! jacobi_solvers.f90:23-31
     allocate(s)
     s%kind = 11
 end function
+
+function hip_multigrid(P, omega, nu_pre, nu_post, coarse_sweeps) result(s)
+    ! V(nu_pre, nu_post) multigrid preconditioner on the Galerkin levels of the prolongations P(1:) (P(l) of shape
+    ! n_{l-1} x n_l; they stay the caller's and must outlive the preconditioner): damped Jacobi sweeps with weight omega,
+    ! coarse_sweeps of them on the last level (sgm_mg_create; an extension, the reference has no multigrid)
+    type(hip_matrix_pointer), intent(in) :: P(:)
+    real(dp), intent(in), optional :: omega
+    integer, intent(in), optional :: nu_pre, nu_post, coarse_sweeps
+    type(hip_linear_solver), pointer :: s
+    type(c_ptr) :: hs(max(size(P), 1))
+    real(dp) :: om
+    integer :: l, n1, n2, nc
+    om = 2.0_dp / 3.0_dp; n1 = 1; n2 = 1; nc = 8
+    if (present(omega)) om = omega
+    if (present(nu_pre)) n1 = nu_pre
+    if (present(nu_post)) n2 = nu_post
+    if (present(coarse_sweeps)) nc = coarse_sweeps
+    hs = c_null_ptr
+    do l = 1, size(P)
+        call P(l)%mat%upload()
+        hs(l) = P(l)%mat%handle
+    enddo
+    allocate(s)
+    s%kind = 13
+    call hip_check(sgm_mg_create(s%handle, int(size(P), c_int32_t), hs, real(om, c_double), int(n1, c_int32_t), &
+                                 int(n2, c_int32_t), int(nc, c_int32_t)))
+end function
+
+subroutine hip_mg_level_info(s, level, nrow, ncol, nnz)
+    ! a multigrid preconditioner that has been set up: the shape of A_level (level 0 = the caller's matrix)
+    class(hip_linear_solver), intent(inout) :: s
+    integer, intent(in) :: level
+    integer, intent(out) :: nrow, ncol
+    integer(c_int64_t), intent(out) :: nnz
+    type(c_ptr) :: h
+    integer(c_int32_t) :: n32, m32, fmt
+    integer(c_int64_t) :: xl
+    call hip_check(sgm_mg_level_matrix(s%handle, int(level, c_int32_t), h))
+    call hip_check(sgm_mat_info(h, n32, m32, nnz, fmt, xl))
+    nrow = n32
+    ncol = m32
+end subroutine
 
 function hip_ldu(incomplete, level, reorder) result(s)      ! ldu_solvers.f90:73-86
     ! reorder = "colour" (extension, off by default): ILDU(0) of the colour-ordered matrix P A P^T (P = greedy_color_ordering of

@@ -358,3 +358,14 @@ def interp2d_csr(nx, ny):
     ptr = np.zeros(n + 1, np.int64)
     np.cumsum(cnt, out=ptr[1:])
     return ((ptr + 1).astype(np.int32), (cols[keep] + 1).astype(np.int32), np.ascontiguousarray(vals[keep]), cx * cy)
+
+
+def interp2d_hierarchy(nx, ny, min_edge=5):
+    """The interp2d_csr prolongations of an nx x ny grid, level after level (each coarse grid is (nx+1)//2 x (ny+1)//2),
+    down to the first grid with an edge below min_edge.  Returns a list of (ptr, node, val, nfine, ncoarse), 1-based."""
+    out = []
+    while min(nx, ny) >= min_edge:
+        ptr, node, val, nc = interp2d_csr(nx, ny)
+        out.append((ptr, node, val, nx * ny, nc))
+        nx, ny = (nx + 1) // 2, (ny + 1) // 2
+    return out
