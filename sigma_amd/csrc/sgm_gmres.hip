@@ -47,17 +47,19 @@ __global__ __launch_bounds__(kBlock) void k_gmres_givens(const double *parts, in
     }
     const double h0 = H[j], h1 = H[j + 1];
     const double d = sqrt(h0 * h0 + h1 * h1);
-    G->cs[j] = h0 / d;
-    G->sn[j] = h1 / d;
-    H[j] = d;
-    H[j + 1] = 0.0;
-    G->g[j + 1] = -G->sn[j] * G->g[j];
-    G->g[j] = G->cs[j] * G->g[j];
-    const double res = fabs(G->g[j + 1]);
+    const double cj = h0 / d, sj = h1 / d, gj = G->g[j];
+    const double res = fabs(sj * gj);
     const int64_t it = *iters;
     if (history && it < hist_cap) history[it] = res * res;
     *iters = it + 1;
     *res_out = res * res;
+    if (res != res) { *flag = 1; return; }      // not a number (0 / 0: A v_j = 0, or a NaN came in): stop, column j stays out of x
+    G->cs[j] = cj;
+    G->sn[j] = sj;
+    H[j] = d;
+    H[j + 1] = 0.0;
+    G->g[j + 1] = -sj * gj;
+    G->g[j] = cj * gj;
     G->j = j + 1;
     if (!(res > tol)) *flag = 1;
 }
@@ -220,7 +222,11 @@ __device__ inline double wave_solve_R(const double *Rl, int kk, double dinv, dou
     return b;
 }
 // after pass 1 (slots g[0..kk-1], t at [kk]): a = (S^T S)^-1 g through R, alpha from Pythagoras (a scale only: what it misses
-// ends up in R), column j of Gs
+// ends up in R), column j of Gs.  t - uu is known to about eps t only: once the new vector is below 1e-8 of |z| it is
+// cancellation noise, zero or negative, and says nothing about whether anything is left of z.  So a difference that is not
+// above 1e-24 t (in practice: not positive) only replaces the SCALE by 1e-12 sqrt(t) (1 when z = 0); pass 2 forms and
+// measures the vector that is really left, and k_gmres_ls2 decides from that measurement whether the Krylov space has closed.
+// t goes along in coef[kk + 1] for that decision.
 __global__ __launch_bounds__(64) void k_gmres_ls1(const double *gt, GmresState *G, const int *flag)
 {
     __shared__ double Rl[33 * kGsLd];
@@ -235,10 +241,16 @@ __global__ __launch_bounds__(64) void k_gmres_ls1(const double *gt, GmresState *
     const double t = __shfl(g, kk), est = t - uu;
     const double alpha = est > 1e-24 * t ? sqrt(est) : (t > 0.0 ? 1e-12 * sqrt(t) : 1.0);
     if (lane < kk) { G->coef[lane] = a; G->Gs[lane + j * 34] = a; }
-    if (lane == kk) { G->coef[kk] = 1.0 / alpha; G->Gs[kk + j * 34] = alpha; }
+    if (lane == kk) { G->coef[kk] = 1.0 / alpha; G->coef[kk + 1] = t; G->Gs[kk + j * 34] = alpha; }
 }
 // after pass 2 (slots c[0..kk-1], d at [kk]): R grows by a column, column j of H = R Gs R^-1 e_j, then the rotations, the residual
-// estimate and the loop test exactly as k_gmres_givens
+// estimate and the loop test exactly as k_gmres_givens.
+// Breakdown ("lucky": the Krylov space has closed) is decided HERE, from the measured vector: alpha^2 (d - rr) is the squared
+// norm of what z has outside the span of the stored columns.  Every entry of z - S a carries a rounding error of at least
+// eps / 2 of |z_i|, so a norm not above eps |z| -- alpha^2 (d - rr) <= eps^2 t, the exact zero of a cyclic shift included -- is
+// nothing: H(j+1, j) = 0 exactly, the rotation reports the residual 0 and the solve ends at this step, as the oracle's does
+// (before, rho = 1 times the made-up alpha left H(j+1, j) = 1e-12 sqrt(t) there, and a solve with tol below that ran on).
+// R still gets its pivot from the fallback below, so R_kk -- all the update of x solves with -- is untouched.
 __global__ __launch_bounds__(64) void k_gmres_ls2(const double *cd, int m, GmresState *G, double tol, int *flag, int64_t *iters,
                                                   double *history, int64_t hist_cap, double *res_out)
 {
@@ -256,6 +268,8 @@ __global__ __launch_bounds__(64) void k_gmres_ls2(const double *cd, int m, Gmres
     const double rr = wave_sum(r * r);
     const double d = __shfl(c, kk), rho2 = d - rr;
     const double rho = rho2 > 1e-24 * d ? sqrt(rho2) : (d > 0.0 ? 1e-12 * sqrt(d) : 1.0);
+    const double alpha = Gl[kk + j * 34];
+    const bool closed = !(alpha * alpha * rho2 > 4.930380657631324e-32 * G->coef[kk + 1]);     // eps^2 t
     if (lane <= kk) {
         const double v = lane < kk ? r : rho;
         Rl[lane + kk * kGsLd] = v;
@@ -271,7 +285,7 @@ __global__ __launch_bounds__(64) void k_gmres_ls2(const double *cd, int m, Gmres
     sacc = 0.0;                                                         // H(:, j) = R_{kk+1} p
     if (lane <= kk)
         for (int l = lane; l <= kk; ++l) sacc += Rl[lane + l * kGsLd] * pv[l];
-    hv[lane] = sacc;
+    hv[lane] = lane == kk && closed ? 0.0 : sacc;
     __syncthreads();
     double *H = G->H + (size_t)j * (m + 1);
     if (lane == 0) {
@@ -283,20 +297,23 @@ __global__ __launch_bounds__(64) void k_gmres_ls2(const double *cd, int m, Gmres
         const double h0 = hv[j], hn = hv[j + 1];
         const double dd = sqrt(h0 * h0 + hn * hn);
         const double cj = h0 / dd, sj = hn / dd;
-        G->cs[j] = cj;
-        G->sn[j] = sj;
-        hv[j] = dd;
-        hv[j + 1] = 0.0;
         const double gj = G->g[j];
-        G->g[j + 1] = -sj * gj;
-        G->g[j] = cj * gj;
         const double res = fabs(sj * gj);
         const int64_t it = *iters;
         if (history && it < hist_cap) history[it] = res * res;
         *iters = it + 1;
         *res_out = res * res;
-        G->j = j + 1;
-        if (!(res > tol)) *flag = 1;
+        if (res != res) *flag = 1;                  // not a number (as k_gmres_givens): stop, column j stays out of x
+        else {
+            G->cs[j] = cj;
+            G->sn[j] = sj;
+            hv[j] = dd;
+            hv[j + 1] = 0.0;
+            G->g[j + 1] = -sj * gj;
+            G->g[j] = cj * gj;
+            G->j = j + 1;
+            if (!(res > tol)) *flag = 1;
+        }
     }
     __syncthreads();
     if (lane <= kk) H[lane] = hv[lane];

@@ -462,7 +462,11 @@ int sgm_solver_solve(sgm_solver s, sgm_mat A, double *x, const double *b, sgm_pc
         fprintf(stderr, "[sigma_hip] cg: %lld iterations on %d rows (> n / 2) with tree-order dot products; validation against the CPU "
                         "build's iteration count: option dot_order = 1 (the reference's summation order, bit-identical iterates)\n",
                 (long long)s->last_iterations, (int)s->nn);
-    if (s->max_iter > 0 && !s->converged) {
+    // GMRES: a residual estimate that is not a number (A v = 0 -- an empty or singular operator --, or a NaN in the data) ends
+    // the solve like the cap does, with or without one: not converged, SGM_ERR_NOT_CONVERGED, x = the last iterate that was a
+    // number (run_gmres keeps the broken column out of the update).  CG / BiCGStab keep the reference's semantics above.
+    const bool gmres_nan = s->kind == SGM_SOLVER_GMRES && s->res2 != s->res2;
+    if ((s->max_iter > 0 || gmres_nan) && !s->converged) {
         if (s->res2 != s->res2) fail(SGM_ERR_NOT_CONVERGED, "solver broke down after %lld iterations (res2 is NaN)", (long long)s->last_iterations);
         else fail(SGM_ERR_NOT_CONVERGED, "solver stopped at max_iter=%lld with sqrt(res2)=%g > %g",
                   (long long)s->max_iter, std::sqrt(s->res2), s->tolerance);
