@@ -21,11 +21,6 @@
 
 namespace sgm {
 
-void free_part(Part &p);
-void set_interior_range(Part &p, const int32_t *ptr1, const int32_t *node1);
-__global__ void k_gather(double *__restrict__ dst, const double *__restrict__ src,
-                         const int32_t *__restrict__ idx, int32_t count);
-
 // ------------------------------------------------------------------ RCCL binding
 struct Rccl {
     void *h = nullptr;
@@ -952,14 +947,6 @@ int sgm_ell_create_dist(sgm_mat *out, sgm_comm comm, const int64_t *row_starts, 
 
 namespace sgm {
 
-struct Staged {
-    double *dev = nullptr;
-    bool owned = false;
-    ~Staged() { if (owned) dfree(dev); }
-};
-int stage_in(Staged &s, const double *v, int64_t n, int where, bool copy);
-int stage_out(const Staged &s, double *v, int64_t n, int where);
-
 // A^T of a matrix distributed over processes, as ANOTHER distributed matrix: every stored entry
 // (row j, column i, value) travels once to the rank that owns column i (counts by all-gather, then one
 // grouped send/recv of three arrays per peer).  Ranks own ascending row blocks and send their entries in
@@ -1114,8 +1101,6 @@ static int ensure_transpose_dist(sgm_mat A)
 // cuts this rank's NEW rows out of the gathered arrays and rebuilds the handle's row block with sgm_csr_create_dist (same row
 // partition, new halo plan).  right_permute needs no exchange at all.  Not for matrices near a rank's memory; what a solver needs
 // per rank without any of this is ldu(reorder = "colour") (sgm_pc.hip).
-
-int sgm_invalidate_transpose(sgm_mat A);          // sgm_layouts.hip
 
 // A device -> host copy of index / value arrays that CHECKS what arrived: the 32-bit words are summed on the device (one atomic
 // per workgroup) and on the host; a copy whose sum differs is waited for (hipDeviceSynchronize) and repeated, loudly.  Setup-path

@@ -391,6 +391,29 @@ int csr_need_arrays(const Part &p);
 int ensure_transpose(sgm_mat A);      // (sgm_mat.hip) A->T and A->tperm built / values refreshed; single-GPU leaves
 void csr_release_arrays(const Part &p);
 
+// A caller vector staged on the device if it lives on the host or is not 16-byte aligned (sgm_mat.hip)
+struct Staged {
+    double *dev = nullptr;
+    bool owned = false;
+    ~Staged() { if (owned) dfree(dev); }
+};
+int stage_in(Staged &s, const double *v, int64_t n, int where, bool copy);
+int stage_out(const Staged &s, double *v, int64_t n, int where);
+
+// sgm_layouts.hip: the kernel forms of a part rebuilt from its CSR / ELLPACK arrays; a part's device memory released; a
+// matrix's cached transpose marked stale
+int rebuild_csr_formats(Part &p);
+int rebuild_ell_formats(Part &p);
+void free_part(Part &p);
+int sgm_invalidate_transpose(sgm_mat A);
+// sgm_spmv.hip: the interior rows [int_lo, int_hi) of a part with a halo, from its 1-based host pattern
+void set_interior_range(Part &p, const int32_t *ptr1, const int32_t *node1);
+// sgm_dist.hip: permutations and the graph of a matrix distributed over ranks (the graph gathered onto every rank, rows
+// moved between ranks); the process-wide switch "dist_force_collectives"
+int permute_dist(sgm_mat A, const int32_t *p_host_global, bool left);
+int gathered_graph(sgm_mat A, sgm_mat *out);
+extern int g_force_collectives;
+
 // sgm_trsv3.hip: slab-pipelined triangular solves for ILDU(0) factors of 3-D grids (deps r-1, r-w, r-w*h)
 struct Slab3;
 int slab3_build(Slab3 **out, int32_t n, const std::vector<int32_t> &Lptr, const std::vector<int32_t> &Lnode,
@@ -411,6 +434,10 @@ void slab3_free(Slab3 *S);
 // ====================================================================== device helpers
 #if defined(__HIPCC__)
 namespace sgm {
+
+// sgm_spmv.hip: dst[t] = src[idx[t]] for t < count -- the one kernel another unit (sgm_dist.hip: the halo send lists) launches by name
+__global__ void k_gather(double *__restrict__ dst, const double *__restrict__ src,
+                         const int32_t *__restrict__ idx, int32_t count);
 
 // Sum over the 64 lanes of a wave, every lane the same bits: the butterfly
 //     for (off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);

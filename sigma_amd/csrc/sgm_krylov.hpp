@@ -14,13 +14,6 @@
 
 namespace sgm {
 
-struct Staged {
-    double *dev = nullptr;
-    bool owned = false;
-    ~Staged() { if (owned) dfree(dev); }
-};
-int stage_in(Staged &s, const double *v, int64_t n, int where, bool copy);
-int stage_out(const Staged &s, double *v, int64_t n, int where);
 int pc_apply_parts(sgm_pc pc, sgm_mat A, const double *const *r, double *const *z, const int *const *flags);
 int pc_kind(sgm_pc pc);
 bool pc_apply_is_short(sgm_pc pc);

@@ -5,11 +5,6 @@
 namespace sgm {
 
 // Stage a caller vector on the device if it lives on the host (or is not 16-B aligned).
-struct Staged {
-    double *dev = nullptr;
-    bool owned = false;
-    ~Staged() { if (owned) dfree(dev); }
-};
 int stage_in(Staged &s, const double *v, int64_t n, int where, bool copy)
 {
     if (where == SGM_DEVICE && (reinterpret_cast<uintptr_t>(v) & 15) == 0) {

@@ -19,12 +19,6 @@
 
 #include <vector>
 
-namespace sgm {
-int rebuild_csr_formats(Part &p);          // sgm_spmv.hip
-void free_part(Part &p);                   // sgm_spmv.hip
-int rebuild_ell_formats(Part &p);          // sgm_spmv.hip
-int sgm_invalidate_transpose(sgm_mat A);   // sgm_spmv.hip
-}
 using namespace sgm;
 
 namespace {
@@ -663,12 +657,6 @@ int halo_attach_order(const Part &p, const int32_t *p1, const std::vector<std::p
     return SGM_OK;
 }
 
-}  // namespace sgm
-
-namespace sgm {
-// (sgm_dist.hip) the same operations on a matrix distributed over ranks: the graph gathered onto every rank, rows moved between ranks
-int permute_dist(sgm_mat A, const int32_t *p_host_global, bool left);
-int gathered_graph(sgm_mat A, sgm_mat *out);
 }  // namespace sgm
 
 extern "C" {

@@ -9,7 +9,6 @@ std::string g_err;
 Runtime g_rt;
 Options g_opt;
 Heartbeat g_hb;
-extern int g_force_collectives;     // sgm_dist.hip
 
 int fail(int code, const char *fmt, ...)
 {
