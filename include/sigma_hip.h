@@ -227,7 +227,9 @@ int sgm_mat_matvec_t_add(sgm_mat A, const double *x, double *y, int where);
  * The edge list (1-based, INSERTION order) is turned into the same ptr/node/val (or
  * node(max_d,n)/val/degrees) arrays on the device -- bit-identical index work.
  * sgm_mat_get reads a leaf matrix back in the reference's layout: "ptr","node","val" (CSR),
- * "max_d","degrees","node","val" (ELLPACK, (max_d,n) Fortran order).                     */
+ * "max_d","degrees","node","val" (ELLPACK, (max_d,n) Fortran order); "versions" (either
+ * format): three int64 -- the handle's serial number, its version (bumped by every change of
+ * its entries or their order) and its pattern_version (bumped by the permutations).      */
 int sgm_csr_from_edges(sgm_mat *out, int32_t nrow, int32_t ncol, int64_t ne, const int32_t *ei_1based,
                        const int32_t *ej_1based, const double *ev, int where);
 int sgm_ell_from_edges(sgm_mat *out, int32_t nrow, int32_t ncol, int64_t ne, const int32_t *ei_1based,
@@ -416,6 +418,39 @@ int sgm_pc_destroy(sgm_pc pc);
 int sgm_mg_create(sgm_pc *out, int32_t ncoarse, const sgm_mat *P /* ncoarse handles, borrowed */,
                   double omega, int32_t nu_pre, int32_t nu_post, int32_t coarse_sweeps);
 int sgm_mg_level_matrix(sgm_pc pc, int32_t level, sgm_mat *borrowed);   /* A_level after setup; level 0 = the caller's A */
+
+/* ---- algebraic coarsening: the prolongations of sgm_mg_create from A alone (an extension, as the multigrid is) ---------- *
+ * Smoothed aggregation on a distance-2 maximal independent set, a contract with one right answer (DESIGN.md section 9d;
+ * restated in tests/aggregate_restated.py).  Indices below are 0-based; the arrays at the boundary are 1-based.
+ *   diagonal     d(i) = the LAST stored copy of a_ii (the Jacobi setup's rule), 0.0 when absent
+ *   strength     a stored entry a of row i in column j != i is strong when a*a >= (theta*theta) * (fabs(d(i)) * fabs(d(j))),
+ *                every product rounded on its own; a NaN on either side: not strong.  N(i) = the set of j with a strong
+ *                stored copy of (i,j) or of (j,i)
+ *   keys         h = (uint32)i * 0x9E3779B1; h ^= h >> 15; h *= 0x85EBCA6B; h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16;
+ *                key(i) = ((uint64)h << 32) | (i + 1)
+ *   roots        the set R with: i in R <=> no j at distance 1 or 2 from i (in N) with key(j) > key(i) is in R -- the
+ *                greedy maximal independent set of the squared graph in descending key order.  Empty N(i): a root
+ *   numbering    roots are numbered 1..nagg in ascending row index
+ *   membership   a root is its own aggregate; phase 1: a non-root with a root in N(i) joins the root of largest key;
+ *                phase 2: every other vertex joins the aggregate of the largest-key member of N(i) that is a root or was
+ *                placed in phase 1
+ *   T            n x nagg, row i holds the one entry (agg(i), 1.0)
+ *   P            smooth_omega == 0: T.  Otherwise W = sgm_mat_product(A, T), every stored value w of W's row i replaced
+ *                by (-(smooth_omega * idiag(i))) * w with idiag(i) = 1.0 / d(i), or 0.0 when d(i) == 0, and
+ *                P = sgm_mat_sum(T, W): T's entry first in every row
+ *   hierarchy    A_0 = A; while levels < max_levels and n_l > min_coarse: aggregate A_l; stop without adding a level when
+ *                nagg >= n_l; otherwise emit P_l and form A_{l+1} = sgm_mat_ptap(A_l, P_l).  *ncoarse = 0 is a valid result
+ * sgm_mat_aggregate writes agg_out[i] in 1..*nagg for every row (n entries, host or device by `where`).
+ * sgm_mg_aggregation_hierarchy returns P_0 .. P_{*ncoarse-1}, new single-GPU CSR matrices the caller owns (sgm_mat_destroy;
+ * they do not depend on A's lifetime); P_out has max_levels-1 slots.  The intermediate A_l are destroyed inside the call
+ * (sgm_pc_setup builds them again).
+ * Refusals: SGM_ERR_DIMS when A is not square; SGM_ERR_UNSUPPORTED for ELLPACK, composite, partitioned or distributed A;
+ * SGM_ERR_BAD_ARG for theta negative or NaN, smooth_omega negative, NaN or infinite, max_levels < 1, min_coarse < 1, null
+ * outputs.  A refused call creates nothing.  A is never modified (its cached transpose may be built).
+ * With SGM_TRACE set the hierarchy prints one line per level on stderr: sizes, rounds and the time of every stage.        */
+int sgm_mat_aggregate(sgm_mat A, double theta, int32_t *agg_out, int32_t *nagg, int where);
+int sgm_mg_aggregation_hierarchy(sgm_mat A, double theta, double smooth_omega, int32_t max_levels, int32_t min_coarse,
+                                 sgm_mat *P_out, int32_t *ncoarse);
 
 /* ---- solvers ------------------------------------------------------------------------ *
  * sgm_cg_create       <- cg(tolerance)            src/solver/cg_solvers.f90:36-47

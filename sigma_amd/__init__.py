@@ -16,6 +16,8 @@ hot path -- same names, argument meaning and error behaviour --
     solver = bicgstab(tolerance)               bicgstab_solvers.f90:37-48
     pc = jacobi(); pc = ldu(incomplete, level) jacobi_solvers.f90:23-31, ldu_solvers.f90:73-86
     pc = multigrid(P, omega, nu_pre, nu_post)  V-cycle on the Galerkin levels of the prolongations P (an extension)
+    agg, nagg = aggregate(A, theta); P = aggregation_hierarchy(A, theta, smooth_omega, max_levels, min_coarse)
+                                               smoothed aggregation: the prolongations from A alone (an extension)
     solver.setup(A); pc.setup(A)
     solver.solve(A, x, b[, pc])                generic solve: linear_solve / linear_solve_pc
     solver.iterations, solver.tolerance, solver.nn, solver.initialized
@@ -863,6 +865,45 @@ def multigrid(P, omega=2.0 / 3.0, nu_pre=1, nu_post=1, coarse_sweeps=8):
     Symmetric positive definite -- valid inside cg -- when nu_pre == nu_post, A is SPD and 0 < omega * lambda_max(D^-1 A) < 2
     (not checked)."""
     return multigrid_solver(P, omega, nu_pre, nu_post, coarse_sweeps)
+
+
+def aggregate(A, theta=0.08, device=False):
+    """(agg, nagg): the aggregates of A's strength graph (sgm_mat_aggregate; include/sigma_hip.h states the contract) --
+    agg[i] in 1..nagg for every row, a numpy array, or an int32 device tensor with device=True."""
+    if hasattr(A, "_build"):
+        A._build()
+    n = int(A.nrow)
+    if device:
+        import torch
+        agg = torch.zeros(max(n, 1), dtype=torch.int32, device="cuda")
+    else:
+        agg = np.zeros(max(n, 1), np.int32)
+    pa, w, _k = _arg(agg, np.int32, writable=True)
+    nagg = C.c_int32(0)
+    _ck(lib().sgm_mat_aggregate(A._h, C.c_double(float(theta)), pa, C.byref(nagg), C.c_int(w)))
+    return agg[:n], nagg.value
+
+
+def aggregation_hierarchy(A, theta=0.08, smooth_omega=2.0 / 3.0, max_levels=25, min_coarse=64):
+    """The prolongations of a smoothed-aggregation hierarchy of A (sgm_mg_aggregation_hierarchy): a list of csr_matrix the
+    caller owns, possibly empty; multigrid(aggregation_hierarchy(A)).setup(A) is the preconditioner built from A alone."""
+    if hasattr(A, "_build"):
+        A._build()
+    slots = max(int(max_levels) - 1, 1)
+    hs = (C.c_void_p * slots)()
+    made = C.c_int32(0)
+    _ck(lib().sgm_mg_aggregation_hierarchy(A._h, C.c_double(float(theta)), C.c_double(float(smooth_omega)),
+                                           C.c_int32(int(max_levels)), C.c_int32(int(min_coarse)), hs, C.byref(made)))
+    out = []
+    for l in range(made.value):
+        M = csr_matrix.__new__(csr_matrix)
+        _Matrix.__init__(M)
+        M._h = C.c_void_p(hs[l])
+        nr, nc, nnz = C.c_int32(0), C.c_int32(0), C.c_int64(0)
+        _ck(lib().sgm_mat_info(M._h, C.byref(nr), C.byref(nc), C.byref(nnz), None, None))
+        M.nrow, M.ncol, M.nnz = nr.value, nc.value, nnz.value
+        out.append(M)
+    return out
 
 
 def ldu(incomplete=True, level=0, reorder=None):

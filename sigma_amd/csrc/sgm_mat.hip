@@ -547,6 +547,7 @@ int sgm_mat_get(sgm_mat A, const char *name, void *out, size_t bytes, size_t *ne
     const std::string nm(name);
     std::vector<int32_t> vi;
     std::vector<double> vd;
+    std::vector<int64_t> vq;
     const bool ell = A->fmt == SGM_FMT_ELL;
     if (!ell && (nm == "node" || nm == "val")) SGM_TRY(csr_need_arrays(p));
     struct Release { const Part &p; bool on; ~Release() { if (on) csr_release_arrays(p); } } rel{p, !ell};
@@ -585,14 +586,16 @@ int sgm_mat_get(sgm_mat A, const char *name, void *out, size_t bytes, size_t *ne
     } else if (nm == "algebra_rows" && A->alg) {      // rows the symbolic pass of sgm_mat_sum / product / ptap / rart ran on the LDS path, the long-row path
         vi.resize(2);
         alg_plan_rows(A->alg, vi.data());
+    } else if (nm == "versions") {                    // what a cached derivative of the matrix compares: serial, version, pattern_version
+        vq = {(int64_t)A->serial, (int64_t)A->version, (int64_t)A->pattern_version};
     } else {
         return fail(SGM_ERR_BAD_ARG, "sgm_mat_get: unknown array '%s' for this format", name);
     }
-    const size_t sz = vi.size() * 4 + vd.size() * 8;
+    const size_t sz = vi.size() * 4 + vd.size() * 8 + vq.size() * 8;
     if (needed) *needed = sz;
     if (out && sz) {
         if (bytes < sz) return fail(SGM_ERR_BAD_ARG, "sgm_mat_get: buffer too small (%zu < %zu)", bytes, sz);
-        memcpy(out, vi.empty() ? (const void *)vd.data() : (const void *)vi.data(), sz);
+        memcpy(out, !vq.empty() ? (const void *)vq.data() : vi.empty() ? (const void *)vd.data() : (const void *)vi.data(), sz);
     }
     return SGM_OK;
 }

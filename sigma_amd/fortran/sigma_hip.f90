@@ -702,6 +702,25 @@ interface
         type(c_ptr), intent(out) :: borrowed       ! A_level after setup (level 0 = the caller's A); not to be destroyed
         integer(c_int) :: rc
     end function
+    function sgm_mat_aggregate(A, theta, agg_out, nagg, where) bind(c, name='sgm_mat_aggregate') result(rc)
+        import :: c_ptr, c_int, c_int32_t, c_double
+        type(c_ptr), value :: A
+        real(c_double), value :: theta
+        integer(c_int32_t), intent(out) :: agg_out(*)      ! nrow aggregate numbers, 1 .. nagg
+        integer(c_int32_t), intent(out) :: nagg
+        integer(c_int), value :: where
+        integer(c_int) :: rc
+    end function
+    function sgm_mg_aggregation_hierarchy(A, theta, smooth_omega, max_levels, min_coarse, P_out, ncoarse) &
+        & bind(c, name='sgm_mg_aggregation_hierarchy') result(rc)
+        import :: c_ptr, c_int, c_int32_t, c_double
+        type(c_ptr), value :: A
+        real(c_double), value :: theta, smooth_omega
+        integer(c_int32_t), value :: max_levels, min_coarse
+        type(c_ptr), intent(out) :: P_out(*)               ! max_levels - 1 slots: new matrices, the caller's
+        integer(c_int32_t), intent(out) :: ncoarse
+        integer(c_int) :: rc
+    end function
     function c_usleep(us) bind(c, name='usleep') result(rc)
         import :: c_int
         integer(c_int), value :: us
@@ -1389,6 +1408,57 @@ subroutine hip_mg_level_info(s, level, nrow, ncol, nnz)
     call hip_check(sgm_mat_info(h, n32, m32, nnz, fmt, xl))
     nrow = n32
     ncol = m32
+end subroutine
+
+subroutine hip_aggregate(A, agg, nagg, theta)
+    ! the aggregates of A's strength graph (sgm_mat_aggregate): agg(i) in 1 .. nagg for every row
+    class(hip_csr_matrix), intent(inout) :: A
+    integer(c_int32_t), intent(out) :: agg(:)
+    integer, intent(out) :: nagg
+    real(dp), intent(in), optional :: theta
+    real(dp) :: th
+    integer(c_int32_t) :: n32
+    th = 0.08_dp
+    if (present(theta)) th = theta
+    call A%upload()
+    call hip_check(sgm_mat_aggregate(A%handle, real(th, c_double), agg, n32, SGM_HOST))
+    nagg = n32
+end subroutine
+
+subroutine hip_aggregation_hierarchy(A, P, ncoarse, theta, smooth_omega, max_levels, min_coarse)
+    ! P(1 : ncoarse) = the prolongations of a smoothed-aggregation hierarchy of A (sgm_mg_aggregation_hierarchy): new
+    ! matrices the caller owns, their host arrays read back from the device; at most size(P) + 1 levels are built.
+    ! hip_multigrid takes them through hip_matrix_pointer like any other prolongation.
+    class(hip_csr_matrix), intent(inout) :: A
+    type(hip_csr_matrix), intent(inout), target :: P(:)
+    integer, intent(out) :: ncoarse
+    real(dp), intent(in), optional :: theta, smooth_omega
+    integer, intent(in), optional :: max_levels, min_coarse
+    type(c_ptr) :: hs(size(P) + 1)
+    real(dp) :: th, om
+    integer :: ml, mc, l
+    integer(c_int32_t) :: made, n32, m32, fmt
+    integer(c_int64_t) :: nnz, xl
+    th = 0.08_dp; om = 2.0_dp / 3.0_dp; ml = 25; mc = 64
+    if (present(theta)) th = theta
+    if (present(smooth_omega)) om = smooth_omega
+    if (present(max_levels)) ml = max_levels
+    if (present(min_coarse)) mc = min_coarse
+    ml = min(ml, size(P) + 1)
+    hs = c_null_ptr
+    call A%upload()
+    call hip_check(sgm_mg_aggregation_hierarchy(A%handle, real(th, c_double), real(om, c_double), int(ml, c_int32_t), &
+                                                int(mc, c_int32_t), hs, made))
+    ncoarse = made
+    do l = 1, ncoarse
+        call P(l)%destroy()
+        P(l)%handle = hs(l)
+        call hip_check(sgm_mat_info(P(l)%handle, n32, m32, nnz, fmt, xl))
+        P(l)%nrow = n32
+        P(l)%ncol = m32
+        allocate(P(l)%ptr(n32 + 1), P(l)%node(nnz), P(l)%val(nnz))
+        call hip_csr_download(P(l))
+    enddo
 end subroutine
 
 function hip_ldu(incomplete, level, reorder) result(s)      ! ldu_solvers.f90:73-86
