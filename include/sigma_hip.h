@@ -161,6 +161,10 @@ int sgm_synchronize(void);
  *                          since -- runs the whole solve in that order (x, b permuted once each way).  A different
  *                          (equally valid) preconditioner than ILDU(0) in A's own order: iteration counts are those of the
  *                          permuted system -- off by default because the reference's `ldu()` factors A in the given order
+ * Multigrid preconditioners take one more name, through sgm_pc_set_option only (SGM_ERR_BAD_ARG on another kind; it is no
+ * process-wide default): "mg_coarse_direct", default 0; 1 = the coarsest level is inverted at the next sgm_pc_setup and every
+ * V-cycle applies the inverse in place of the coarse sweeps (at most SGM_MG_DIRECT_MAX_ROWS rows; see sgm_mg_create below).
+ * Like "ildu_reorder" it selects a different preconditioner, not another kernel for the same bits.
  * Process-wide (sgm_set_option only)
  *   "dist_force_collectives" (0)  1 = a matrix distributed over ONE rank still issues its all-reduces (the fixed cost of the
  *                          RCCL code path, measurable on a single-GPU box: bench.py's `dist_overhead_1rank`)          */
@@ -414,7 +418,23 @@ int sgm_pc_destroy(sgm_pc pc);
  * sgm_pc_info: out4 = {levels, levels, 5, 0}, path_name e.g. "V(1,1) omega 0.8, 7 levels, 8 coarse sweeps".
  * sgm_pc_get: "mg_paths" (int32 per level: 1 = sweeps fused on the 4-bit sliced form, 2 = fused on the 1-byte sliced form (rows of up to 9 or 27 entries),
  * 0 = product + elementwise pass), "mg_idiag_<l>" (the inverse diagonal of level l).
- * sgm_mg_level_matrix: A_level after setup (level 0 = the caller's A), borrowed: do not destroy it.                        */
+ * sgm_mg_level_matrix: A_level after setup (level 0 = the caller's A), borrowed: do not destroy it.
+ *
+ * Direct coarse solve: sgm_pc_set_option(pc, "mg_coarse_direct", 1) -- default 0, read at the next
+ * sgm_pc_setup, SGM_ERR_BAD_ARG on a preconditioner of another kind.  Setup then inverts the coarsest level A_L on the
+ * device by dense Gauss-Jordan elimination with partial pivoting, and every V-cycle replaces the coarse sweeps by the one
+ * dense product x = Ainv b (with no prolongation at all the preconditioner is A^-1 itself):
+ *   D(i,j) = +0.0 plus the stored copies of (i,j) in stored order; W = [D | I]; for k = 0 .. n-1:
+ *     p = the smallest i >= k that maximises fabs(W(i,k)) (a NaN counts as the largest); piv(k) = p + 1; rows k and p swapped;
+ *     W(k,j) = W(k,j) / W(k,k) (the divisor taken first); every i != k: f = W(i,k), W(i,j) = W(i,j) - (f * W(k,j))
+ *   Ainv = the right block.  x(i) = +0.0 plus s_0(i), s_1(i), ... where s_c(i) = +0.0 plus the individually rounded products
+ *   Ainv(i,j) * b(j) of the columns 256c .. 256c+255 in ascending j.
+ * Setup refuses with SGM_ERR_UNSUPPORTED when A_L has more than SGM_MG_DIRECT_MAX_ROWS rows (the message gives both numbers)
+ * and when a pivot W(p,k) is 0, NaN or +-Inf ("singular or non-finite coarse level", the message names the 1-based step).
+ * sgm_pc_get: "mg_coarse_inverse" (n * n doubles, row-major), "mg_coarse_pivots" (n int32, 1-based); both SGM_ERR_BAD_ARG
+ * when the last successful setup ran without the option ("mg_coarse_invert_ms": one double, the time of the last inversion).  sgm_pc_info: path_name ends with "direct coarse solve (1297 rows)"
+ * in place of "8 coarse sweeps".  A second setup inverts again; the option may change between setups.                      */
+#define SGM_MG_DIRECT_MAX_ROWS 4096   /* a 128 MiB inverse, plus twice that as elimination workspace during setup */
 int sgm_mg_create(sgm_pc *out, int32_t ncoarse, const sgm_mat *P /* ncoarse handles, borrowed */,
                   double omega, int32_t nu_pre, int32_t nu_post, int32_t coarse_sweeps);
 int sgm_mg_level_matrix(sgm_pc pc, int32_t level, sgm_mat *borrowed);   /* A_level after setup; level 0 = the caller's A */

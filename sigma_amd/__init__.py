@@ -16,6 +16,7 @@ hot path -- same names, argument meaning and error behaviour --
     solver = bicgstab(tolerance)               bicgstab_solvers.f90:37-48
     pc = jacobi(); pc = ldu(incomplete, level) jacobi_solvers.f90:23-31, ldu_solvers.f90:73-86
     pc = multigrid(P, omega, nu_pre, nu_post)  V-cycle on the Galerkin levels of the prolongations P (an extension)
+                                               coarse="direct": the last level inverted at setup, applied as a dense product
     agg, nagg = aggregate(A, theta); P = aggregation_hierarchy(A, theta, smooth_omega, max_levels, min_coarse)
                                                smoothed aggregation: the prolongations from A alone (an extension)
     solver.setup(A); pc.setup(A)
@@ -824,12 +825,16 @@ class multigrid_solver(_Preconditioner):
     """One V-cycle on Galerkin levels with damped Jacobi sweeps (sgm_mg_create; include/sigma_hip.h states the contract)."""
     _kind = 3       # SGM_PC_MG
 
-    def __init__(self, P, omega, nu_pre, nu_post, coarse_sweeps):
+    def __init__(self, P, omega, nu_pre, nu_post, coarse_sweeps, coarse="sweeps"):
+        if coarse not in ("sweeps", "direct"):
+            raise ValueError(f'multigrid: coarse is "sweeps" or "direct", not {coarse!r}')
         super().__init__()
         self.P = list(P)            # borrowed by the library: kept alive here
         hs = (C.c_void_p * max(len(self.P), 1))(*[p._h for p in self.P])
         _ck(lib().sgm_mg_create(C.byref(self._h), C.c_int32(len(self.P)), hs, C.c_double(float(omega)),
                                 C.c_int32(int(nu_pre)), C.c_int32(int(nu_post)), C.c_int32(int(coarse_sweeps))))
+        if coarse == "direct":
+            self.set_option("mg_coarse_direct", 1)
 
     @property
     def levels(self):
@@ -857,14 +862,25 @@ class multigrid_solver(_Preconditioner):
     def idiag(self, level):
         return self.get(f"mg_idiag_{int(level)}", np.float64)
 
+    def coarse_inverse(self):
+        """the n x n inverse of the coarsest level (option "mg_coarse_direct" / coarse="direct"), as setup computed it"""
+        a = self.get("mg_coarse_inverse", np.float64)
+        n = int(round(np.sqrt(a.size)))
+        return a.reshape(n, n)
 
-def multigrid(P, omega=2.0 / 3.0, nu_pre=1, nu_post=1, coarse_sweeps=8):
+    def coarse_pivots(self):
+        """the pivot rows of that elimination, 1-based: piv[k] = the row swapped with row k + 1 at step k + 1"""
+        return self.get("mg_coarse_pivots", np.int32)
+
+
+def multigrid(P, omega=2.0 / 3.0, nu_pre=1, nu_post=1, coarse_sweeps=8, coarse="sweeps"):
     """V(nu_pre, nu_post) multigrid preconditioner on the Galerkin hierarchy of the prolongations P (a list of csr_matrix,
     P[l] of shape n_l x n_{l+1}; an empty list = the coarse sweeps on A alone): damped Jacobi sweeps with weight omega,
     coarse_sweeps of them on the last level.  An extension: the reference has PtAP "for multigrid setup" and no multigrid.
     Symmetric positive definite -- valid inside cg -- when nu_pre == nu_post, A is SPD and 0 < omega * lambda_max(D^-1 A) < 2
-    (not checked)."""
-    return multigrid_solver(P, omega, nu_pre, nu_post, coarse_sweeps)
+    (not checked).  coarse="direct": the last level (at most 4096 rows) is inverted at setup -- dense Gauss-Jordan with
+    partial pivoting on the device -- and every V-cycle applies that inverse in place of the coarse sweeps."""
+    return multigrid_solver(P, omega, nu_pre, nu_post, coarse_sweeps, coarse)
 
 
 def aggregate(A, theta=0.08, device=False):

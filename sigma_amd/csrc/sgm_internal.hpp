@@ -263,6 +263,7 @@ int mg_apply_vectors(MgState *S, const double *r, double *z, int where);    // s
 int mg_get(MgState *S, const char *name, const void **src, size_t *sz);     // "mg_paths", "mg_idiag_<l>"
 int mg_info(MgState *S, int32_t out4[4], double *est_us, char *name, size_t len);
 void mg_free(MgState *S);
+int mg_set_option(MgState *S, const char *name, int value);                 // "mg_coarse_direct": read at the next setup
 sgm_pc pc_adopt_mg(MgState *S);
 MgState *pc_mg(sgm_pc pc);         // null: not a multigrid preconditioner
 }

@@ -5,7 +5,8 @@
 // copy of the diagonal, 0.0 when absent).  z = M^-1 r is vcycle(0, r):
 //   first sweep (from the zero start)   x(i) = omega * (idiag(i) * b(i))
 //   every further sweep, out of place   q = A_l x ; t(i) = b(i) - q(i) ; x'(i) = x(i) + omega * (idiag(i) * t(i))
-//   l == L                              coarse_sweeps sweeps
+//   l == L                              coarse_sweeps sweeps -- or, with option "mg_coarse_direct", x = Ainv b with the dense
+//                                       inverse of A_L made at setup (sgm_mg_direct.hip)
 //   otherwise                           nu_pre sweeps ; r = b - A_l x ; b_c = P_l^T r (the transposed product's order) ;
 //                                       x_c = vcycle(l + 1, b_c) ; x = x + (0.0 + P_l x_c) ; nu_post sweeps
 // Every operation is rounded on its own (-ffp-contract=off); a row sum is the library's matvec sum: +0.0 plus the
@@ -19,6 +20,7 @@
 // operands in the same order: the same bits.
 #include "sgm_spmv_select.hpp"
 #include "sgm_krylov.hpp"
+#include "sgm_pc_internal.hpp"
 
 #include <chrono>
 
@@ -45,6 +47,8 @@ struct MgState {
     bool refilled = false;
     std::vector<int32_t> hpaths;   // sgm_pc_get staging
     std::vector<double> hidiag;
+    int direct_opt = 0;            // option "mg_coarse_direct": read at setup
+    MgDirect *direct = nullptr;    // the inverse of the coarsest level when the last setup ran with the option (else null)
 };
 
 // ------------------------------------------------------------------ kernels
@@ -347,6 +351,11 @@ static int vcycle(MgState *S, int l, const double *b, double *first, double *sec
     const int L = (int)S->lev.size() - 1;
     const MgLevel &Lv = S->lev[(size_t)l];
     double *cur = first, *other = second;
+    if (l == L && S->direct) {                          // x = Ainv b in place of the coarse sweeps
+        SGM_TRY(mg_direct_apply(S->direct, b, first, flag));
+        *res = first;
+        return SGM_OK;
+    }
     if (Lv.n) launch_elem(Lv.n, FMgFirst{b, Lv.idiag, cur, S->omega}, flag);
     const int sweeps = l == L ? S->coarse : S->nu_pre;
     for (int s = 1; s < sweeps; ++s) {
@@ -392,6 +401,8 @@ static void free_levels(MgState *S)
         if (l > 0 && S->lev[l].A) sgm_mat_destroy(S->lev[l].A);
     }
     S->lev.clear();
+    mg_direct_free(S->direct);
+    S->direct = nullptr;
     S->ready = false;
 }
 void mg_free(MgState *S)
@@ -470,6 +481,9 @@ int mg_setup(MgState *S, sgm_mat A)
         for (size_t l = 0; l < L; ++l) S->p_pattern[l] = S->P[l]->pattern_version;
     }
     for (auto &Lv : S->lev) SGM_TRY(level_idiag(Lv));
+    mg_direct_free(S->direct);
+    S->direct = nullptr;
+    if (S->direct_opt) SGM_TRY(mg_direct_setup(&S->direct, S->lev[L].A));
     SGM_HIP(hipStreamSynchronize(g_rt.stream));
     S->setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     S->ready = true;
@@ -479,6 +493,7 @@ int mg_setup(MgState *S, sgm_mat A)
         mg_info(S, o, &us, nm, sizeof nm);
         fprintf(stderr, "[sigma_hip] multigrid setup (%s, %.2f ms): %s, about %.0f us per apply\n", S->refilled ? "refill" : "build",
                 S->setup_ms, nm, us);
+        if (S->direct) fprintf(stderr, "[sigma_hip] multigrid coarse inversion: %d rows, %.2f ms\n", mg_direct_rows(S->direct), mg_direct_invert_ms(S->direct));
     }
     return SGM_OK;
 }
@@ -491,7 +506,7 @@ int mg_apply(MgState *S, const double *r, double *z, const int *flag)
     MgLevel &L0 = S->lev[0];
     if (L0.n == 0) return SGM_OK;
     const bool coarse_only = S->lev.size() == 1;
-    const int swaps = coarse_only ? S->coarse - 1 : S->nu_pre - 1 + S->nu_post;
+    const int swaps = coarse_only ? (S->direct ? 0 : S->coarse - 1) : S->nu_pre - 1 + S->nu_post;
     const double *b = r;
     if (r == z) {
         SGM_HIP(hipMemcpyAsync(L0.b, r, (size_t)L0.n * 8, hipMemcpyDeviceToDevice, g_rt.stream));
@@ -526,6 +541,16 @@ int mg_get(MgState *S, const char *name, const void **src, size_t *sz)
         *src = S->hpaths.data(); *sz = S->hpaths.size() * 4;
         return SGM_OK;
     }
+    if (nm == "mg_coarse_invert_ms") {                  // host clock around the last inversion, its final synchronisation included
+        if (!S->direct) return fail(SGM_ERR_BAD_ARG, "sgm_pc_get: '%s' needs option mg_coarse_direct at the last setup", name);
+        S->hidiag.assign(1, mg_direct_invert_ms(S->direct));
+        *src = S->hidiag.data(); *sz = 8;
+        return SGM_OK;
+    }
+    if (nm == "mg_coarse_inverse" || nm == "mg_coarse_pivots") {
+        if (!S->direct) return fail(SGM_ERR_BAD_ARG, "sgm_pc_get: '%s' needs option mg_coarse_direct at the last setup", name);
+        return mg_direct_get(S->direct, name, src, sz);
+    }
     if (nm.rfind("mg_idiag_", 0) == 0 && nm.size() > 9 && nm.find_first_not_of("0123456789", 9) == std::string::npos && nm.size() < 19) {
         const long l = atol(nm.c_str() + 9);
         if (l >= (long)S->lev.size()) return fail(SGM_ERR_BAD_ARG, "sgm_pc_get: '%s': the hierarchy has %zu levels", name, S->lev.size());
@@ -551,6 +576,11 @@ int mg_info(MgState *S, int32_t out4[4], double *est_us, char *nm, size_t len)
         int64_t mv = 0;
         (void)sgm_mat_footprint(Lv.A, nullptr, &mv);
         const bool fused = Lv.n && mg_path(Lv.A->parts[0]);
+        if (l == nl - 1 && S->direct) {                                            // one dense product
+            bytes += 8.0 * Lv.n * Lv.n + 16.0 * Lv.n;
+            launches += 1;
+            continue;
+        }
         const int passes = l == nl - 1 ? S->coarse - 1 : S->nu_pre - 1 + S->nu_post;
         bytes += 24.0 * Lv.n;                                                      // the sweep from the zero start
         bytes += passes * ((double)mv + (fused ? 16.0 : 40.0) * Lv.n);             // b, idiag (+ q written and read, x read again)
@@ -565,8 +595,18 @@ int mg_info(MgState *S, int32_t out4[4], double *est_us, char *nm, size_t len)
     }
     if (out4) { out4[0] = nl; out4[1] = nl; out4[2] = 5; out4[3] = 0; }
     if (est_us) *est_us = bytes / 5.5e6 + 4.5 * launches;
-    if (nm && len) snprintf(nm, len, "V(%d,%d) omega %g, %d level%s, %d coarse sweep%s", S->nu_pre, S->nu_post, S->omega, nl,
+    if (nm && len && S->direct)
+        snprintf(nm, len, "V(%d,%d) omega %g, %d level%s, direct coarse solve (%d rows)", S->nu_pre, S->nu_post, S->omega, nl,
+                 nl == 1 ? "" : "s", mg_direct_rows(S->direct));
+    else if (nm && len) snprintf(nm, len, "V(%d,%d) omega %g, %d level%s, %d coarse sweep%s", S->nu_pre, S->nu_post, S->omega, nl,
                             nl == 1 ? "" : "s", S->coarse, S->coarse == 1 ? "" : "s");
+    return SGM_OK;
+}
+
+int mg_set_option(MgState *S, const char *name, int value)
+{
+    if (!S || strcmp(name, "mg_coarse_direct")) return fail(SGM_ERR_BAD_ARG, "sgm_pc_set_option: '%s' is not a multigrid option", name);
+    S->direct_opt = value != 0;
     return SGM_OK;
 }
 

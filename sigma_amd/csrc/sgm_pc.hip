@@ -527,6 +527,10 @@ int sgm_ildu0_create(sgm_pc *out, sgm_mat A)
 int sgm_pc_set_option(sgm_pc pc, const char *name, int value)
 {
     if (!pc || !name) return fail(SGM_ERR_BAD_ARG, "sgm_pc_set_option: null argument");
+    if (!strcmp(name, "mg_coarse_direct")) {            // the multigrid group: one name, kept by the hierarchy's state
+        if (pc->kind != SGM_PC_MG) return fail(SGM_ERR_BAD_ARG, "sgm_pc_set_option: '%s' is an option of multigrid preconditioners", name);
+        return mg_set_option(pc->mg, name, value);
+    }
     int v = 0;
     SGM_TRY(normalise_option(name, value, &v));
     int *f = pc_option_field(pc->opt, name);

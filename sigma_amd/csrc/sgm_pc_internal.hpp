@@ -1,7 +1,8 @@
 // Private to the preconditioner family: sgm_pc.hip (the object, Jacobi, the colour re-ordering, the pc_* functions of the
 // Krylov loops, the C ABI), sgm_ildu.hip (ILDU(0) setup) and sgm_trsv.hip (the triangular sweeps).  The state of an ILDU(0)
 // preconditioner and the host functions the three call across; sgm_trsv3.hip (the slab pipeline) keeps its own state behind
-// the slab3_* functions of sgm_internal.hpp.  The library is built without relocatable device code: a kernel is launched
+// the slab3_* functions of sgm_internal.hpp; sgm_mg.hip and sgm_mg_direct.hip share the mg_direct_* functions at the end.
+// The library is built without relocatable device code: a kernel is launched
 // only from the file that defines it, so everything declared here is a host function.
 #pragma once
 #include "sgm_internal.hpp"
@@ -199,5 +200,14 @@ void apply_rows(const IlduState *S, const double *r, double *z, const int *flag)
 void rows_cg_fused(const IlduState *S, ScalarRef res2, ScalarRef dpr, const double *q, double *r, double *z, double *part, int *count,
                    const int *flag, int gen);
 void scale_by(int64_t n, const double *d, const double *r, double *z, const int *flag);      // z = d * r: the Jacobi apply
+
+// ---- sgm_mg_direct.hip: the dense inverse of multigrid's coarsest level, used by sgm_mg.hip
+struct MgDirect;
+int mg_direct_setup(MgDirect **out, sgm_mat A);      // Gauss-Jordan with partial pivoting; a refusal leaves *out null
+int mg_direct_apply(const MgDirect *D, const double *b, double *x, const int *flag);      // x = Ainv b, b != x, stream-ordered
+int mg_direct_get(MgDirect *D, const char *name, const void **src, size_t *sz);           // "mg_coarse_inverse" / "mg_coarse_pivots"
+int mg_direct_rows(const MgDirect *D);
+double mg_direct_invert_ms(const MgDirect *D);
+void mg_direct_free(MgDirect *D);
 
 }  // namespace sgm

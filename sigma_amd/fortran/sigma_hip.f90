@@ -1368,13 +1368,16 @@ function hip_jacobi() result(s)                    ! jacobi_solvers.f90:23-31
     s%kind = 11
 end function
 
-function hip_multigrid(P, omega, nu_pre, nu_post, coarse_sweeps) result(s)
+function hip_multigrid(P, omega, nu_pre, nu_post, coarse_sweeps, coarse_direct) result(s)
     ! V(nu_pre, nu_post) multigrid preconditioner on the Galerkin levels of the prolongations P(1:) (P(l) of shape
     ! n_{l-1} x n_l; they stay the caller's and must outlive the preconditioner): damped Jacobi sweeps with weight omega,
-    ! coarse_sweeps of them on the last level (sgm_mg_create; an extension, the reference has no multigrid)
+    ! coarse_sweeps of them on the last level (sgm_mg_create; an extension, the reference has no multigrid).
+    ! coarse_direct = .true.: the last level (at most 4096 rows) is inverted at setup and every V-cycle applies that inverse
+    ! in place of the coarse sweeps (option "mg_coarse_direct")
     type(hip_matrix_pointer), intent(in) :: P(:)
     real(dp), intent(in), optional :: omega
     integer, intent(in), optional :: nu_pre, nu_post, coarse_sweeps
+    logical, intent(in), optional :: coarse_direct
     type(hip_linear_solver), pointer :: s
     type(c_ptr) :: hs(max(size(P), 1))
     real(dp) :: om
@@ -1393,6 +1396,9 @@ function hip_multigrid(P, omega, nu_pre, nu_post, coarse_sweeps) result(s)
     s%kind = 13
     call hip_check(sgm_mg_create(s%handle, int(size(P), c_int32_t), hs, real(om, c_double), int(n1, c_int32_t), &
                                  int(n2, c_int32_t), int(nc, c_int32_t)))
+    if (present(coarse_direct)) then
+        if (coarse_direct) call hip_check(sgm_pc_set_option(s%handle, 'mg_coarse_direct' // c_null_char, 1_c_int))
+    endif
 end function
 
 subroutine hip_mg_level_info(s, level, nrow, ncol, nnz)
