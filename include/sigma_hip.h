@@ -48,7 +48,7 @@ enum {
 };
 enum { SGM_HOST = 0, SGM_DEVICE = 1 };
 enum { SGM_FMT_CSR = 1, SGM_FMT_ELL = 2, SGM_FMT_COMPOSITE = 3 };
-enum { SGM_SOLVER_CG = 1, SGM_SOLVER_BICGSTAB = 2, SGM_SOLVER_GMRES = 3 };
+enum { SGM_SOLVER_CG = 1, SGM_SOLVER_BICGSTAB = 2, SGM_SOLVER_GMRES = 3, SGM_SOLVER_MINRES = 4 };
 enum { SGM_PC_JACOBI = 1, SGM_PC_ILDU0 = 2 };
 #define SGM_PC_MG 3        /* multigrid V-cycle: made by sgm_mg_create (it needs its prolongations), not by sgm_pc_create */
 
@@ -124,12 +124,14 @@ int sgm_synchronize(void);
  *                          size k; 0 = modified Gram-Schmidt (k + 2 dependent passes and reductions, 4 k + 8 vector passes),
  *                          the checker.  (Round 4's blocked CGS-2 with the second projection applied -- three passes, three
  *                          reductions -- was 1265 it/s on C3 against 1644 and is gone.)
- *   "dot_order" (0)        how CG / BiCGStab add up their dot products.  0 = tree order (per-workgroup partial sums,
+ *   "dot_order" (0)        how CG / BiCGStab / MINRES add up their dot products.  0 = tree order (per-workgroup partial sums,
  *                          re-reduced in a fixed order): a legal order for the Fortran intrinsic, deterministic, the fast one.
  *                          1 = the order the reference build uses (amdflang -O2 turns dot_product into ONE accumulator fed
  *                          first element to last, cg_solvers.f90:131,135,140): every iterate, iteration count and residual is
  *                          then BIT-IDENTICAL to the reference's, also on row partitions and across ranks; about 4 ns per
- *                          element -- a VALIDATION mode for n up to ~1e5.  GMRES (no reference counterpart) keeps the tree order
+ *                          element -- a VALIDATION mode for n up to ~1e5.  MINRES (no reference counterpart) takes the same
+ *                          one-accumulator order with 1, which makes its whole solve deterministic down to the bit
+ *                          (sgm_minres_create states every operation).  GMRES (no reference counterpart) keeps the tree order
  *   "coop_spin_limit" (0 = built-in, 2^19 polls)  how often a hand-off of the cooperative CG / BiCGStab kernels polls before
  *                          it gives up (the launch loop then takes the solve from the caller's x); tests set 1 to force that path
  *   "cg_coop_variant" (0)  which cooperative kernel serves a system, all the same statements: low four bits = rows per thread
@@ -479,6 +481,41 @@ int sgm_mg_aggregation_hierarchy(sgm_mat A, double theta, double smooth_omega, i
  *                        classical Gram-Schmidt with re-orthogonalisation (CGS-2: the basis read twice, two
  *                        reductions per step; option "gmres_cgs2" = 0: modified Gram-Schmidt), Givens
  *                        rotations; same tolerance / iterations conventions as cg
+ * sgm_minres_create   <- NO reference counterpart; preconditioned MINRES (Paige-Saunders) for SYMMETRIC A, definite or not,
+ *                        and a symmetric positive definite preconditioner M (neither property is checked): one product per
+ *                        step, seven work vectors whatever the step count, a residual norm that never increases.  Single-GPU
+ *                        CSR, ELLPACK and composite matrices, every preconditioner kind or none; sgm_solver_setup refuses
+ *                        row-partitioned and distributed matrices with SGM_ERR_UNSUPPORTED.  The contract (DESIGN.md 9f;
+ *                        tests/minres_restated.py restates it) -- every operation rounded on its own, `A u` the library's
+ *                        product (0.0 + row sum in stored order), `a.b` the solver's dot product (tree order; ONE accumulator
+ *                        fed first element to last with option "dot_order" = 1, and then every bit of the solve is pinned),
+ *                        `M^-1 u` a copy without a preconditioner:
+ *                            r1 = b - A x ; y = M^-1 r1 ; beta1 = sqrt(r1.y)
+ *                            beta1 == 0: return (0 iterations, res2 = 0, converged)
+ *                            oldb = 0 ; beta = beta1 ; dbar = 0 ; epsln = 0 ; phibar = beta1 ; cs = -1 ; sn = 0
+ *                            w = w2 = 0 ; r2 = r1
+ *                            while fabs(phibar) > tolerance (and the max_iter cap allows), k = 1, 2, ...:
+ *                                s = 1.0/beta ; v(i) = s*y(i)
+ *                                y = A v
+ *                                k >= 2:  t = beta/oldb ; y(i) = y(i) - t*r1(i)
+ *                                alfa = v.y
+ *                                t = alfa/beta ; y(i) = y(i) - t*r2(i)
+ *                                r1 = r2 ; r2 = y ; y = M^-1 r2
+ *                                oldb = beta ; bb = r2.y ; beta = sqrt(bb)
+ *                                oldeps = epsln ; delta = cs*dbar + sn*alfa ; gbar = sn*dbar - cs*alfa
+ *                                epsln = sn*beta ; dbar = -(cs*beta)
+ *                                gamma = sqrt(gbar*gbar + beta*beta) ; gi = 1.0/gamma ; cs = gbar*gi ; sn = beta*gi
+ *                                phi = cs*phibar ; phibar = sn*phibar
+ *                                w1 = w2 ; w2 = w ; w(i) = ((v(i) - oldeps*w1(i)) - delta*w2(i)) * gi ; x(i) = x(i) + phi*w(i)
+ *                                iterations += 1 ; history gets fabs(phibar)
+ *                            res2 = phibar*phibar
+ *                        Tolerance (ABSOLUTE, on sqrt(res2) = |phibar|, the M^-1-norm of the residual as in cg_solve_pc),
+ *                        max_iter, `iterations`, `converged` as for cg; the history holds fabs(phibar), not its square.  beta == 0
+ *                        after a step is convergence (sn = 0, phibar = 0).  Ends that are NOT convergence: bb < 0 (M is not
+ *                        positive definite) or bb not a number -- at the start or in a step --, gamma == 0, gamma or phibar not
+ *                        a number.  The solve stops AT that step: the step is not counted, x keeps the value it had before it,
+ *                        the call returns SGM_OK (with or without a cap) and converged = 0; res2 is NaN, or the last
+ *                        phibar*phibar for gamma == 0.
  * sgm_solver_setup    <- solver%setup(A): square check, work vectors, iterations = 0
  *                        cg_solvers.f90:52-90
  * sgm_solver_solve    <- solver%solve(A,x,b[,pc]): cg_solve :116-150, cg_solve_pc :155-194,
@@ -498,6 +535,7 @@ int sgm_mg_aggregation_hierarchy(sgm_mat A, double theta, double smooth_omega, i
 int sgm_cg_create(sgm_solver *out, double tolerance);
 int sgm_bicgstab_create(sgm_solver *out, double tolerance);
 int sgm_gmres_create(sgm_solver *out, double tolerance, int32_t restart);
+int sgm_minres_create(sgm_solver *out, double tolerance);
 int sgm_solver_setup(sgm_solver s, sgm_mat A);
 int sgm_solver_set_max_iter(sgm_solver s, int64_t max_iter /* <= 0: unbounded */);
 int sgm_solver_set_tolerance(sgm_solver s, double tolerance);

@@ -14,6 +14,7 @@ hot path -- same names, argument meaning and error behaviour --
                                                (scalars or ordered batches, edited in HBM); edit_plan(A, i, j).add(z)
     solver = cg(tolerance)                     cg_solvers.f90:36-47
     solver = bicgstab(tolerance)               bicgstab_solvers.f90:37-48
+    solver = gmres(tolerance, restart); solver = minres(tolerance)         extensions: GMRES(m); MINRES for symmetric indefinite A
     pc = jacobi(); pc = ldu(incomplete, level) jacobi_solvers.f90:23-31, ldu_solvers.f90:73-86
     pc = multigrid(P, omega, nu_pre, nu_post)  V-cycle on the Galerkin levels of the prolongations P (an extension)
                                                coarse="direct": the last level inverted at setup, applied as a dense product
@@ -951,8 +952,8 @@ class _Solver:
         raise NotImplementedError
 
     def set_option(self, name, value):
-        """sgm_solver_set_option: this solver's own "cg_small" / "bicgstab_small" / "krylov_graph" / "dot_order" /
-        "gmres_cgs2" (read at the next solve)."""
+        """sgm_solver_set_option: this solver's own "cg_small" / "bicgstab_small" / "krylov_graph" / "dot_order" (CG, BiCGStab,
+        MINRES) / "gmres_cgs2" (read at the next solve)."""
         self._opts[name] = int(value)
         if self._h:
             _ck(lib().sgm_solver_set_option(self._h, name.encode(), C.c_int(int(value))))
@@ -1068,6 +1069,11 @@ class gmres_solver(_Solver):
         _ck(lib().sgm_gmres_create(C.byref(self._h), C.c_double(self.tolerance), C.c_int32(self.restart)))
 
 
+class minres_solver(_Solver):
+    def _create(self):
+        _ck(lib().sgm_minres_create(C.byref(self._h), C.c_double(self.tolerance)))
+
+
 def cg(tolerance=None):
     """cg(tolerance) factory (cg_solvers.f90:36-47); default tolerance 1e-16 (:106)."""
     return cg_solver(tolerance)
@@ -1081,6 +1087,15 @@ def bicgstab(tolerance=None):
 def gmres(tolerance=None, restart=30):
     """GMRES(restart).  Not in the reference; conventions follow cg."""
     return gmres_solver(tolerance, restart)
+
+
+def minres(tolerance=1e-16):
+    """Preconditioned MINRES (Paige-Saunders) for symmetric A, definite or not, and a symmetric positive definite
+    preconditioner (sgm_minres_create; include/sigma_hip.h states the contract).  Not in the reference; conventions follow cg,
+    except that the history holds |phibar| = sqrt(res2).  Single-GPU csr_matrix, ellpack_matrix and sparse_matrix operands;
+    with set_option("dot_order", 1) the whole solve is pinned bit for bit.  A step that cannot be finished (the preconditioner
+    is not positive definite, a NaN) ends the solve without raising: `converged` is then False."""
+    return minres_solver(tolerance)
 
 
 # ------------------------------------------------------------------------------------ #

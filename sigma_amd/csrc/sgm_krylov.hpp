@@ -1,5 +1,5 @@
 // Shared by the Krylov translation units (sgm_solvers.hip: solver object, dots, C ABI; sgm_cg.hip; sgm_bicgstab.hip;
-// sgm_gmres.hip; sgm_lanczos.hip): the generic fused vector kernel and its launcher, the functors more than one loop uses,
+// sgm_gmres.hip; sgm_minres.hip; sgm_lanczos.hip): the generic fused vector kernel and its launcher, the functors more than one loop uses,
 // the solver object and the helpers every loop calls.  Kernels defined here are `static`: each unit launches its own copy.
 #pragma once
 #include "sgm_internal.hpp"
@@ -332,6 +332,13 @@ struct FScaleInv {
     __device__ void single(int64_t i) { dst[i] = src[i] / d; }
     __device__ void finish(double *) {}
 };
+// ---- MINRES ----------------------------------------------------------------------------
+// lives in device memory: the recurrence's scalars (sgm_minres.hip: MS_OLDB ...), twice -- step k reads copy k & 1 and leaves
+// copy (k + 1) & 1 -- and why a solve ended without converging (0: it did not)
+struct MinresDev {
+    double st[2][8];
+    int32_t fail;
+};
 // ---- dot_order = 1: the reference's dot_product order -----------------------------------------------------
 // The pinned reference build (amdflang -O2, x86-64 without FMA) turns `dot_product(a, b)` into ONE accumulator that
 // starts at +0.0 and takes the individually rounded products a(i) * b(i) first element to last
@@ -428,6 +435,7 @@ struct PartWork {
     double *res = nullptr;           // device: last res2
     double *history = nullptr;
     GmresState *gmres = nullptr;
+    MinresDev *minres = nullptr;
     double *V = nullptr;             // GMRES basis, (restart+1) x next
     int count[kNumPartials] = {0};   // producer grid of each partial array
 };
@@ -444,6 +452,7 @@ struct sgm_solver_s {
     int64_t last_iterations = 0;
     double res2 = 0.0;
     int32_t converged = 0;
+    int32_t breakdown = 0;           // MINRES: the last solve stopped at a step it could not finish (run_minres); not an error, not converged
     bool seq = false;                // this solve runs with dot_order = 1 (set by sgm_solver_solve from the option)
     int32_t *abort_dev = nullptr;    // the preconditioner's sticky abort word while its pipelined sweeps are in use (sgm_pc.hip)
     int32_t aborted = 0;             // ... as last read by read_state: nonzero = this solve's iterates are spoiled, stop and redo
@@ -519,5 +528,6 @@ bool graph_applies(sgm_solver s, sgm_mat A, sgm_pc pc);
 int run_cg(sgm_solver s, sgm_mat A, double *const *x, const double *const *b, sgm_pc pc);
 int run_bicgstab(sgm_solver s, sgm_mat A, double *const *x, const double *const *b, sgm_pc pc);
 int run_gmres(sgm_solver s, sgm_mat A, double *const *x, const double *const *b, sgm_pc pc);
+int run_minres(sgm_solver s, sgm_mat A, double *const *x, const double *const *b, sgm_pc pc);
 
 }  // namespace sgm

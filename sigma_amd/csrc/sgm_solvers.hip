@@ -1,5 +1,5 @@
 // Device-resident Krylov loops for gfx950: CG / PCG (cg_solvers.f90:116-194), BiCGStab /
-// preconditioned BiCGStab (bicgstab_solvers.f90:124-237) and GMRES(m) (no reference
+// preconditioned BiCGStab (bicgstab_solvers.f90:124-237), GMRES(m) and MINRES (no reference
 // counterpart), plus the dot / axpy statements they are made of.
 //
 // Design: the whole `do while (dsqrt(res2) > tolerance)` loop runs on the GPU.
@@ -99,14 +99,14 @@ __global__ __launch_bounds__(kBlock) void k_reduce_set(ReduceSet rs)
 }
 
 
-int num_work_vectors(int kind) { return kind == SGM_SOLVER_CG ? 4 : kind == SGM_SOLVER_BICGSTAB ? 8 : 3; }
+int num_work_vectors(int kind) { return kind == SGM_SOLVER_CG ? 4 : kind == SGM_SOLVER_BICGSTAB ? 8 : kind == SGM_SOLVER_MINRES ? 7 : 3; }
 
 void free_work(sgm_solver s)
 {
     for (auto &w : s->work) {
         for (double *v : w.vec) dfree(v);
         dfree(w.partials); dfree(w.slots); dfree(w.flag); dfree(w.iters); dfree(w.res);
-        dfree(w.history); dfree(w.gmres); dfree(w.V);
+        dfree(w.history); dfree(w.gmres); dfree(w.minres); dfree(w.V);
     }
     s->work.clear();
     dfree(s->x_backup);
@@ -269,6 +269,7 @@ int sgm_gmres_create(sgm_solver *out, double tolerance, int32_t restart)
         return fail(SGM_ERR_BAD_ARG, "sgm_gmres_create: restart must be in 1..%d", kGmresMaxRestart);
     return solver_create(out, SGM_SOLVER_GMRES, tolerance, restart);
 }
+int sgm_minres_create(sgm_solver *out, double tolerance) { return solver_create(out, SGM_SOLVER_MINRES, tolerance, 0); }
 
 // solver%tolerance is a public field the reference's loops read at every solve (`do while( dsqrt(res2)>solver%tolerance )`,
 // cg_solvers.f90:133,175; bicgstab_solvers.f90:153) and set_params may be called again (cg_solvers.f90:95-111): the tolerance of
@@ -288,7 +289,14 @@ int sgm_solver_setup(sgm_solver s, sgm_mat A)
     if (!s || !A) return fail(SGM_ERR_BAD_ARG, "sgm_solver_setup: null argument");
     if (A->nrow != A->ncol)     // cg_solvers.f90:61-65
         return fail(SGM_ERR_DIMS, "Cannot make a %s solver for a non-square matrix",
-                    s->kind == SGM_SOLVER_CG ? "CG" : s->kind == SGM_SOLVER_BICGSTAB ? "BiCGStab" : "GMRES");
+                    s->kind == SGM_SOLVER_CG ? "CG" : s->kind == SGM_SOLVER_BICGSTAB ? "BiCGStab" : s->kind == SGM_SOLVER_MINRES ? "MINRES" : "GMRES");
+    if (s->kind == SGM_SOLVER_MINRES) {
+        bool split = A->distributed();
+        for (const sgm_mat_s *B : A->blocks) split = split || (B && B->distributed());
+        if (split)
+            return fail(SGM_ERR_UNSUPPORTED, "MINRES runs on a single-GPU matrix (CSR, ELLPACK or a composite of them): "
+                                             "row-partitioned and distributed matrices are not supported");
+    }
     s->nn = A->nrow;
     s->iterations = 0;          // cg_solvers.f90:72
     s->multi = A->distributed();
@@ -314,6 +322,7 @@ int sgm_solver_setup(sgm_solver s, sgm_mat A)
             SGM_TRY(dalloc(&w.flag, 1));
             SGM_TRY(dalloc(&w.iters, 1));
             SGM_TRY(dalloc(&w.res, 1));
+            if (s->kind == SGM_SOLVER_MINRES) SGM_TRY(dalloc(&w.minres, 1));
             if (s->kind == SGM_SOLVER_GMRES) {
                 SGM_TRY(dalloc(&w.gmres, 1));
                 SGM_TRY(dalloc(&w.V, (size_t)(s->restart + 1) * w.next + 2));
@@ -386,8 +395,8 @@ int sgm_solver_solve(sgm_solver s, sgm_mat A, double *x, const double *b, sgm_pc
         }
         if (w.history) SGM_HIP(hipMemsetAsync(w.history, 0, (size_t)s->hist_cap * 8, g_rt.stream));
     }
-    // dot_order = 1: CG / BiCGStab add their dot products in the reference's order (GMRES has no reference counterpart
-    // and keeps the tree order)
+    // dot_order = 1: CG / BiCGStab add their dot products in the reference's order, MINRES in that same order (GMRES has no
+    // reference counterpart and keeps the tree order)
     s->seq = s->opt.dot_order == 1 && s->kind != SGM_SOLVER_GMRES;
     // A pipelined ILDU sweep has bounded waits; one that gives up leaves NaN patterns behind and raises the preconditioner's
     // sticky word.  It is read with every look at the stop flag (read_state); if it was raised the iterates are spoiled:
@@ -424,6 +433,7 @@ int sgm_solver_solve(sgm_solver s, sgm_mat A, double *x, const double *b, sgm_pc
     for (int attempt = 0; attempt < 2; ++attempt) {
         if (s->kind == SGM_SOLVER_CG) rc = run_cg(s, Arun, xs.data(), bs.data(), pc);
         else if (s->kind == SGM_SOLVER_BICGSTAB) rc = run_bicgstab(s, Arun, xs.data(), bs.data(), pc);
+        else if (s->kind == SGM_SOLVER_MINRES) rc = run_minres(s, Arun, xs.data(), bs.data(), pc);
         else rc = run_gmres(s, Arun, xs.data(), bs.data(), pc);
         if (rc != SGM_OK) return rc;
         if (!s->aborted) break;
@@ -466,7 +476,10 @@ int sgm_solver_solve(sgm_solver s, sgm_mat A, double *x, const double *b, sgm_pc
     // the solve like the cap does, with or without one: not converged, SGM_ERR_NOT_CONVERGED, x = the last iterate that was a
     // number (run_gmres keeps the broken column out of the update).  CG / BiCGStab keep the reference's semantics above.
     const bool gmres_nan = s->kind == SGM_SOLVER_GMRES && s->res2 != s->res2;
-    if ((s->max_iter > 0 || gmres_nan) && !s->converged) {
+    // MINRES: a step that could not be finished (M not positive definite, gamma == 0, a NaN) ends the solve with SGM_OK and
+    // converged = 0, capped or not; only the cap itself is SGM_ERR_NOT_CONVERGED
+    const bool minres_end = s->kind == SGM_SOLVER_MINRES && s->breakdown;
+    if ((s->max_iter > 0 || gmres_nan) && !s->converged && !minres_end) {
         if (s->res2 != s->res2) fail(SGM_ERR_NOT_CONVERGED, "solver broke down after %lld iterations (res2 is NaN)", (long long)s->last_iterations);
         else fail(SGM_ERR_NOT_CONVERGED, "solver stopped at max_iter=%lld with sqrt(res2)=%g > %g",
                   (long long)s->max_iter, std::sqrt(s->res2), s->tolerance);

@@ -11,6 +11,8 @@
 !   A%matvec / A%matvec_add                   same names                   !
 !     linear_operator_interface.f90:185-194                                !
 !   cg(tol), bicgstab(tol)  cg_solvers.f90:36 hip_cg(tol), hip_bicgstab()  !
+!   (nothing: extensions)                     hip_gmres(tol, restart),     !
+!                                               hip_minres(tol)            !
 !   jacobi(), ldu()     jacobi_solvers.f90:23 hip_jacobi(), hip_ldu()      !
 !   solver%setup(A), solver%solve(A,x,b[,pc]), solver%destroy()            !
 !   solver%iterations, %tolerance, %nn, %initialized                       !
@@ -356,6 +358,13 @@ interface
         type(c_ptr), intent(out) :: s
         real(c_double), value :: tolerance
         integer(c_int32_t), value :: restart
+        integer(c_int) :: rc
+    end function
+    function sgm_minres_create(s, tolerance) &
+            & bind(c, name='sgm_minres_create') result(rc)
+        import :: c_ptr, c_int, c_double
+        type(c_ptr), intent(out) :: s
+        real(c_double), value :: tolerance
         integer(c_int) :: rc
     end function
     function sgm_solver_setup(s, A) bind(c, name='sgm_solver_setup') result(rc)
@@ -904,7 +913,7 @@ type :: hip_linear_solver                                                  !
     logical :: initialized = .false.
     integer :: iterations = 0
     real(dp) :: tolerance = 1.0d-16
-    integer :: kind = 0          ! 1 cg, 2 bicgstab, 3 gmres, 11 jacobi, 12 ldu
+    integer :: kind = 0          ! 1 cg, 2 bicgstab, 3 gmres, 4 minres, 11 jacobi, 12 ldu
     integer :: restart = 30
     type(c_ptr) :: handle = c_null_ptr
 contains
@@ -1362,6 +1371,14 @@ function hip_gmres(tolerance, restart) result(s)   ! no reference counterpart
     if (present(restart)) s%restart = restart
 end function
 
+function hip_minres(tolerance) result(s)          ! no reference counterpart: symmetric A, definite or not
+    real(dp), intent(in), optional :: tolerance
+    type(hip_linear_solver), pointer :: s
+    allocate(s)
+    s%kind = 4
+    if (present(tolerance)) s%tolerance = tolerance
+end function
+
 function hip_jacobi() result(s)                    ! jacobi_solvers.f90:23-31
     type(hip_linear_solver), pointer :: s
     allocate(s)
@@ -1492,6 +1509,8 @@ subroutine hip_solver_make_handle(s)
         call hip_check(sgm_bicgstab_create(s%handle, s%tolerance))
     case (3)
         call hip_check(sgm_gmres_create(s%handle, s%tolerance, int(s%restart, c_int32_t)))
+    case (4)
+        call hip_check(sgm_minres_create(s%handle, s%tolerance))
     case (11)
         call hip_check(sgm_pc_create(s%handle, 1_c_int32_t))
     case (12)
