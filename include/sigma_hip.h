@@ -214,6 +214,18 @@ int sgm_ell_create(sgm_mat *out, int32_t nrow, int32_t ncol, int32_t max_d,
 int sgm_ell_set_values(sgm_mat A, const double *val_colmajor, int where);
 int sgm_mat_matvec(sgm_mat A, const double *x, double *y, int where);
 int sgm_mat_matvec_add(sgm_mat A, const double *x, double *y, int where);
+/* sgm_mat_matvec_dots: test introspection -- y = A x (add = 1: y += A x, not chained, like sgm_mat_matvec_add) launched with
+ * the fused dot epilogues exactly as the solvers launch it (CG's p.Ap, BiCGStab's r0.v / t.s / t.t, Lanczos's q.Aq in the
+ * default dot order), and the scalars those epilogues leave, per part, as a consumer would see them: every part's partial
+ * sums collapsed by the solvers' own reducer (k_reduce = load_scalar: same sum, same order).
+ *   w and yy_out: both dots; w (and wy_out) only: w.y; yy_out only (w null): y.y; neither: SGM_ERR_BAD_ARG.
+ *   wy_out / yy_out / count_out: HOST arrays, one entry per part (one entry for a single matrix or a composite);
+ *   count_out[ip] = the number of partial sums part ip's product leaves per dot.
+ * Vectors as for sgm_mat_matvec (w laid out like y), `where` holds for x, y and w.  Single-GPU CSR / ELLPACK matrices,
+ * in-process partitions and composites of single-GPU leaves; a matrix on a communicator is SGM_ERR_UNSUPPORTED, and so
+ * is w on a non-square matrix (y.y alone is fine there).  The partial arrays are allocated per call and start as NaN.   */
+int sgm_mat_matvec_dots(sgm_mat A, const double *x, double *y, const double *w_or_null, int add,
+                        double *wy_out_or_null, double *yy_out_or_null, int32_t *count_out_or_null, int where);
 /* sgm_mat_matvec_t     <- A%matvec_t(x,y): y = 0 ; matvec_t_add
  *                         src/linear_operator/linear_operator_interface.f90:199-208
  * sgm_mat_matvec_t_add <- csc_matvec_add (the csr transpose kernel) cs_matrices.f90:627-647 /

@@ -216,6 +216,33 @@ class _Matrix:
         _ck(lib().sgm_mat_matvec_add(self._h, px, py, C.c_int(_same_where(wx, wy))))
         return y
 
+    def matvec_dots(self, x, y, w=None, add=False, yy=True):
+        """sgm_mat_matvec_dots (test introspection): y = A x (add: y += A x) launched with the fused dot epilogues the
+        solvers use, and what they leave per part: (wy, yy, count), numpy arrays of length nparts -- sum(w * y), sum(y * y)
+        as a consumer kernel would reduce the partial sums, and how many partial sums there are; None where a dot was not
+        asked for (w=None: no w.y; yy=False: no y.y)."""
+        if hasattr(self, "_build"):
+            self._build()
+        nx, ny = self._lens()
+        _need(x, nx, "matvec_dots x"); _need(y, ny, "matvec_dots y")
+        px, wx, _k1 = _arg(x, np.float64)
+        py, wy_, _k2 = _arg(y, np.float64, writable=True)
+        ws = [wx, wy_]
+        pw = None
+        if w is not None:
+            _need(w, ny, "matvec_dots w")
+            pw, ww, _k3 = _arg(w, np.float64)
+            ws.append(ww)
+        P = getattr(self, "nparts", 1)
+        o_wy = np.zeros(P, np.float64) if w is not None else None
+        o_yy = np.zeros(P, np.float64) if yy else None
+        cnt = np.zeros(P, np.int32)
+        _ck(lib().sgm_mat_matvec_dots(self._h, px, py, pw, C.c_int(1 if add else 0),
+                                      C.c_void_p(o_wy.ctypes.data) if o_wy is not None else None,
+                                      C.c_void_p(o_yy.ctypes.data) if o_yy is not None else None,
+                                      C.c_void_p(cnt.ctypes.data), C.c_int(_same_where(*ws))))
+        return o_wy, o_yy, cnt
+
     # -- linear_operator_interface.f90:199-208 ------------------------------------------
     def matvec_t(self, x, y):
         _need(x, getattr(self, "n_local", self.nrow), "matvec_t x"); _need(y, getattr(self, "nc_local", self.ncol), "matvec_t y")
@@ -585,6 +612,7 @@ class partitioned_csr_matrix(_Matrix):
         val = np.ascontiguousarray(val, np.float64)
         rs = np.ascontiguousarray(row_starts, np.int64)
         self.nrow, self.ncol, self.nnz = int(nrow), int(ncol), int(len(val))
+        self.nparts = len(rs) - 1
         _ck(lib().sgm_csr_create_partitioned(C.byref(self._h), C.c_int32(len(rs) - 1), C.c_void_p(rs.ctypes.data),
                                              C.c_int32(nrow), C.c_int32(ncol), C.c_int64(self.nnz),
                                              C.c_void_p(ptr.ctypes.data), C.c_void_p(node.ctypes.data),
@@ -613,6 +641,7 @@ class partitioned_csr_matrix(_Matrix):
             pp[k], pn[k], pv[k] = p1, p2, p3
             nnz[k] = int(len(c))
         self.nrow = self.ncol = int(rs[-1])
+        self.nparts = P
         self.nnz = int(sum(nnz))
         _ck(lib().sgm_csr_create_partitioned_parts(C.byref(self._h), C.c_int32(P), C.c_void_p(rs.ctypes.data), nnz, pp, pn, pv,
                                                    C.c_int(_same_where(*wheres))))

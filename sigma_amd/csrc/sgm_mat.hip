@@ -1,6 +1,7 @@
 // Matrix handles of the C ABI (include/sigma_hip.h): create / set_values / products and transpose products / composite /
 // getters, and the staging of caller vectors.
 #include "sgm_spmv_select.hpp"
+#include "sgm_krylov.hpp"      // k_reduce: the reducer the consumers of a fused dot use (sgm_mat_matvec_dots)
 
 namespace sgm {
 
@@ -251,6 +252,62 @@ static int matvec_impl(sgm_mat A, const double *x, double *y, int where, bool ad
     return finish();
 }
 
+// sgm_mat_matvec_dots: matvec_impl with a SpmvDots, as the solvers launch it (CG p.Ap, BiCGStab r0.v / t.s / t.t, Lanczos q.Aq),
+// and every part's partial sums collapsed by k_reduce -- load_scalar's sum, the bits a consumer kernel would see.  The partial
+// arrays are the call's own and start as NaN: a slot inside a part's count that no workgroup wrote shows in the scalar.
+static int matvec_dots_impl(sgm_mat A, const double *x, double *y, const double *w, bool add, double *wy_out, double *yy_out,
+                            int32_t *count_out, int where)
+{
+    SGM_TRY(require_init());
+    if (!A || !x || !y) return fail(SGM_ERR_BAD_ARG, "matvec_dots: null argument");
+    if ((w != nullptr) != (wy_out != nullptr) || (!w && !yy_out))
+        return fail(SGM_ERR_BAD_ARG, "matvec_dots: ask for w.y (w and wy_out), y.y (yy_out) or both");
+    if (A->comm) return fail(SGM_ERR_UNSUPPORTED, "matvec_dots: not available on a matrix distributed over processes");
+    if (w && A->nrow != A->ncol) return fail(SGM_ERR_UNSUPPORTED, "matvec_dots: w.y needs a square matrix (y.y alone does not)");
+    const size_t P = A->parts.size();
+    const bool one = P == 1;            // (a composite is one part of nrow x ncol)
+    const int64_t nx = one ? A->parts[0].xlen() : A->ncol, ny = one ? A->parts[0].n : A->nrow;
+    struct Bufs { double *part = nullptr; ~Bufs() { dfree(part); } } m;      // per part: kMaxGrid partials per dot; then 2 slots per part
+    SGM_TRY(dalloc(&m.part, 2 * P * ((size_t)kMaxGrid + 1)));
+    SGM_HIP(hipMemsetAsync(m.part, 0xFF, 2 * P * ((size_t)kMaxGrid + 1) * 8, g_rt.stream));
+    double *slots = m.part + 2 * P * (size_t)kMaxGrid;
+    Staged sx, sy, sw;
+    SGM_TRY(stage_in(sx, x, nx, where, true));
+    SGM_TRY(stage_in(sy, y, ny, where, add));
+    if (w) SGM_TRY(stage_in(sw, w, ny, where, true));
+    std::vector<const double *> xs(P), ws(P);
+    std::vector<double *> ys(P), pw(P), py(P);
+    for (size_t ip = 0; ip < P; ++ip) {
+        Part &p = A->parts[ip];
+        if (!one) SGM_HIP(hipMemcpyAsync(p.xext, sx.dev + p.row_begin, (size_t)p.ncol_own * 8, hipMemcpyDeviceToDevice, g_rt.stream));
+        xs[ip] = one ? sx.dev : p.xext;
+        ys[ip] = sy.dev + (one ? 0 : p.row_begin);
+        ws[ip] = w ? sw.dev + (one ? 0 : p.row_begin) : nullptr;
+        pw[ip] = m.part + (2 * ip) * (size_t)kMaxGrid;
+        py[ip] = m.part + (2 * ip + 1) * (size_t)kMaxGrid;
+    }
+    SpmvDots dots;
+    if (w) { dots.w = ws.data(); dots.part_wy = pw.data(); }
+    if (yy_out) dots.part_yy = py.data();
+    SGM_TRY(spmv_parts(A, xs.data(), ys.data(), add, &dots, nullptr, nullptr));
+    for (size_t ip = 0; ip < P; ++ip) {
+        const int count = spmv_grid(A->parts[ip]);
+        if (count_out) count_out[ip] = count;
+        if (w) hipLaunchKernelGGL(k_reduce, dim3(1), dim3(kBlock), 0, g_rt.stream, (const double *)pw[ip], count, slots + 2 * ip);
+        if (yy_out) hipLaunchKernelGGL(k_reduce, dim3(1), dim3(kBlock), 0, g_rt.stream, (const double *)py[ip], count, slots + 2 * ip + 1);
+    }
+    SGM_HIP(hipGetLastError());
+    std::vector<double> h(2 * P);
+    SGM_HIP(hipMemcpyAsync(h.data(), slots, 2 * P * 8, hipMemcpyDeviceToHost, g_rt.stream));
+    SGM_TRY(stage_out(sy, y, ny, where));
+    SGM_HIP(hipStreamSynchronize(g_rt.stream));
+    for (size_t ip = 0; ip < P; ++ip) {
+        if (w) wy_out[ip] = h[2 * ip];
+        if (yy_out) yy_out[ip] = h[2 * ip + 1];
+    }
+    return SGM_OK;
+}
+
 // y = A x on device vectors laid out like sgm_mat_matvec's: one part (also one rank of a distributed matrix: x holds
 // [owned | halo room]) or an in-process partition (plain global vectors); stream-ordered, no synchronisation
 int matvec_plain(sgm_mat A, const double *x, double *y)
@@ -456,6 +513,12 @@ int sgm_mat_matvec(sgm_mat A, const double *x, double *y, int where)
 int sgm_mat_matvec_add(sgm_mat A, const double *x, double *y, int where)
 {
     return matvec_impl(A, x, y, where, true);
+}
+
+int sgm_mat_matvec_dots(sgm_mat A, const double *x, double *y, const double *w_or_null, int add, double *wy_out_or_null,
+                        double *yy_out_or_null, int32_t *count_out_or_null, int where)
+{
+    return matvec_dots_impl(A, x, y, w_or_null, add != 0, wy_out_or_null, yy_out_or_null, count_out_or_null, where);
 }
 
 int sgm_composite_create(sgm_mat *out, int32_t nrb, int32_t ncb, const int32_t *row_ptr, const int32_t *col_ptr,

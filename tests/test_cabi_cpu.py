@@ -125,6 +125,7 @@ NOT_FOR_A_FORTRAN_HOST = {
     "sgm_dist_neighbors_host": "same",
     "sgm_partition_links_host": "same",
     "sgm_mat_halo_nbr": "reads the exchange plan of a built matrix back for the parity tests",
+    "sgm_mat_matvec_dots": "reads the fused partial sums of a product back for the parity tests",
     "sgm_slice_sched_host": "the slice schedule as a host table, so that a CPU test can check it is a permutation",
     "sgm_ell_degrees_host": "host-only index work (the degrees of an ELLPACK graph from its padding), exported for the CPU tests",
     "sgm_left_permute_rows_host": "host-only index work (a rank's rows of a permuted matrix), exported for the CPU tests",
