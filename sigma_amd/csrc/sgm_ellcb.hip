@@ -25,7 +25,7 @@
 //
 // (Round 3 also ran the two phases band by band over one product buffer sized for the Infinity Cache -- measured slower,
 // profiles/r03/c4_row_bands_kernel_stats.txt, and removed in round 4; the products make their round trip through HBM.)
-#include "sgm_internal.hpp"
+#include "sgm_spmv_device.hpp"
 
 #include <hipcub/hipcub.hpp>
 
@@ -164,7 +164,7 @@ __global__ __launch_bounds__(TPB) void k_ellcb_mul(int32_t ncol, int32_t cb, int
                                                    const int *__restrict__ flag_done, int gen)
 {
     extern __shared__ double xs[];
-    if (flag_done) { const int st = *flag_done; if (st && gen >= st) return; }
+    if (stopped(flag_done, gen)) return;
     const int32_t lo = blockIdx.x / chunks, c = blockIdx.x % chunks;
     const int64_t j0b = bstart[lo], j1b = bstart[lo + 1], len = j1b - j0b;
     int64_t j0 = j0b + (len * c / chunks), j1 = j0b + (len * (c + 1) / chunks);
@@ -242,7 +242,7 @@ __global__ __launch_bounds__(TPB) void k_ellcb_sum(int32_t n, int32_t max_d, int
 {
     extern __shared__ double img[];
     __shared__ double red[TPB / 64];
-    if (flag_done) { const int st = *flag_done; if (st && gen >= st) return; }
+    if (stopped(flag_done, gen)) return;
     constexpr int NW = TPB / 64;
     const int lane = threadIdx.x & 63, half = FULLW ? 0 : lane >> 5, q = FULLW ? lane : lane & 31;
     constexpr int RW = FULLW ? 64 : 32;          // lanes per run
@@ -287,26 +287,18 @@ __global__ __launch_bounds__(TPB) void k_ellcb_sum(int32_t n, int32_t max_d, int
         if (live) {
             double y0 = 0.0;
             if (ADD) y0 = y[i];
-            double z = (ADD && chain) ? y0 : 0.0;
+            double z = row_start<ADD>(y0, chain);
 #pragma unroll
             for (int k = 0; k < MAXD; ++k)
                 if (k < deg) z = z + img[pz[k]];
             for (int32_t k = MAXD; k < deg; ++k) z = z + img[lpos[(int64_t)k * n + i]];
-            const double yi = ADD ? (chain ? z : y0 + z) : 0.0 + z;
+            const double yi = row_value<ADD>(y0, z, chain);
             y[i] = yi;
-            if (DOT_W) dwy += w[i] * yi;
-            if (DOT_YY) dyy += yi * yi;
+            dots_add<DOT_W, DOT_YY>(DOT_W ? w[i] : 0.0, yi, dwy, dyy);
         }
         __syncthreads();
     }
-    if (DOT_W) {
-        const double s = block_sum<TPB>(dwy, red);
-        if (threadIdx.x == 0) part_wy[blockIdx.x] = s;
-    }
-    if (DOT_YY) {
-        const double s = block_sum<TPB>(dyy, red);
-        if (threadIdx.x == 0) part_yy[blockIdx.x] = s;
-    }
+    dots_write<TPB, DOT_W, DOT_YY>(dwy, dyy, red, part_wy, part_yy);
 }
 
 // ------------------------------------------------------------------------------ host side
@@ -458,31 +450,25 @@ int build_ell_colblock(Part &p)
     return SGM_OK;
 }
 
-template <int R, bool ADD>
-static void launch_sum(const Part &p, int grid, double *y, const double *w, double *pwy, double *pyy, const int *flag, int gen, int chain)
+template <int R>
+static void launch_sum(const Part &p, int grid, const SpmvArgs &a)
 {
-    hipStream_t st = g_rt.stream;
     const size_t lds = (size_t)p.cb_R * p.cb_maxd * 8;
     constexpr bool BIG = R == 512;                   // 128 KiB image, 1024 threads, whole-wave runs
     constexpr int MAXD = (BIG ? 16384 : 8192) / R;   // the longest row a tile of R rows allows
     constexpr int TPB = BIG ? 1024 : 2 * R;          // twice as many waves copy runs as there are rows (C4: 696 -> see DESIGN)
-#define L(DW, DY)                                                                                                     \
-    do {                                                                                                              \
-        static bool attr = false;                                                                                     \
-        if (BIG && !attr) { (void)hipFuncSetAttribute((const void *)k_ellcb_sum<R, TPB, MAXD, ADD, DW, DY, BIG>, hipFuncAttributeMaxDynamicSharedMemorySize, R * MAXD * 8); attr = true; } \
-        hipLaunchKernelGGL((k_ellcb_sum<R, TPB, MAXD, ADD, DW, DY, BIG>), dim3(grid), dim3(TPB), lds, st, p.n, p.cb_maxd, p.cb_nb, p.cb_ntiles, \
-                           (const int2 *)p.cb_fdesc, (const uint16_t *)p.cb_lpos, (const double *)p.cb_P, y, w, pwy, pyy, flag, gen, chain, \
-                           cb_from_csr(p) ? (const int32_t *)p.rowptr : (const int32_t *)nullptr); \
-    } while (0)
-    if (w && pyy) L(true, true);
-    else if (w) L(true, false);
-    else if (pyy) L(false, true);
-    else L(false, false);
-#undef L
+    with_flags(a, [&](auto flags) {
+        using F = decltype(flags);
+        static bool attr = false;
+        if (BIG && !attr) { (void)hipFuncSetAttribute((const void *)k_ellcb_sum<R, TPB, MAXD, F::add, F::dot_w, F::dot_yy, BIG>, hipFuncAttributeMaxDynamicSharedMemorySize, R * MAXD * 8); attr = true; }
+        hipLaunchKernelGGL((k_ellcb_sum<R, TPB, MAXD, F::add, F::dot_w, F::dot_yy, BIG>), dim3(grid), dim3(TPB), lds, g_rt.stream, p.n, p.cb_maxd, p.cb_nb,
+                           p.cb_ntiles, (const int2 *)p.cb_fdesc, (const uint16_t *)p.cb_lpos, (const double *)p.cb_P, a.y, a.w, a.pwy,
+                           a.pyy, a.flag, a.gen, a.add && a.chain ? 1 : 0,
+                           cb_from_csr(p) ? (const int32_t *)p.rowptr : (const int32_t *)nullptr);
+    });
 }
 
-int launch_ell_colblock(const Part &p, int grid, const double *x, double *y, bool add, bool chain, const double *w,
-                        double *pwy, double *pyy, const int *flag, int gen)
+int launch_ell_colblock(const Part &p, int grid, const SpmvArgs &a)
 {
     hipStream_t st = g_rt.stream;
     constexpr int TPB1 = 512, U1 = 4;      // (1024 threads x 4: 571 us on C4 against 559: the stream is not short of loads in flight)
@@ -492,13 +478,9 @@ int launch_ell_colblock(const Part &p, int grid, const double *x, double *y, boo
         attr_set = true;
     }
     hipLaunchKernelGGL((k_ellcb_mul<TPB1, U1>), dim3(p.cb_nb * p.cb_chunks), dim3(TPB1), (size_t)p.cb_cols * 8, st, p.ncol_own, p.cb_cols,
-                       p.cb_nb, p.cb_chunks, (const int32_t *)p.cb_bstart, (const double *)p.cb_sval, (const uint16_t *)p.cb_lcol, x, p.cb_P,
-                       flag, gen);
-#define R_CASE(RR)                                                                              \
-    if (p.cb_R == RR) {                                                                         \
-        if (add) launch_sum<RR, true>(p, grid, y, w, pwy, pyy, flag, gen, chain ? 1 : 0);        \
-        else launch_sum<RR, false>(p, grid, y, w, pwy, pyy, flag, gen, 0);                       \
-    }
+                       p.cb_nb, p.cb_chunks, (const int32_t *)p.cb_bstart, (const double *)p.cb_sval, (const uint16_t *)p.cb_lcol, a.x, p.cb_P,
+                       a.flag, a.gen);
+#define R_CASE(RR) if (p.cb_R == RR) launch_sum<RR>(p, grid, a);
     R_CASE(64) R_CASE(128) R_CASE(192) R_CASE(256) R_CASE(512)
 #undef R_CASE
     SGM_HIP(hipGetLastError());

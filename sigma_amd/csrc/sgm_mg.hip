@@ -13,12 +13,12 @@
 // individually rounded products in stored order.
 //
 // Hot path: a level whose matrix holds the 4-bit sliced form (k_csr_sl's: sval / scode / dict) or the 1-byte sliced form
-// (k_csr_slb's: sval / sbcode / dict; widths 9 and 27) runs a sweep -- or the residual -- as ONE kernel: the row sum formed exactly as
-// k_csr_sl / k_csr_slb form it (same slot order, same 16-byte loads, two adjacent rows per lane), then the epilogue on the
+// (k_csr_slb's: sval / sbcode / dict; widths 9 and 27) runs a sweep -- or the residual -- as ONE kernel: the row sum formed by the functions
+// k_csr_sl / k_csr_slb form it with (sl_row_sums / slb_row_sums, sgm_spmv_device.hpp; two adjacent rows per lane), then the epilogue on the
 // lane's own rows.  Against product + elementwise pass that saves q's write and read (16 bytes per row) and a launch.  Any
 // other layout runs the composition: spmv_parts into a scratch q, then one k_elem functor.  Same operations on the same
 // operands in the same order: the same bits.
-#include "sgm_spmv_select.hpp"
+#include "sgm_spmv_device.hpp"
 #include "sgm_krylov.hpp"
 #include "sgm_pc_internal.hpp"
 
@@ -114,16 +114,6 @@ struct FMgResid {
 
 enum { MG_SMOOTH = 0, MG_RESID = 1 };
 
-// the slice a workgroup starts with: round-robin, or k_csr_sl's XCD-block-cyclic map with groups of 32 (the launcher asks
-// for it only when the grid is a multiple of 256: the map is then a permutation)
-__device__ inline int64_t mg_first_slice(int remap)
-{
-    if (!remap) return blockIdx.x;
-    constexpr int G = 32;
-    const int xcd = blockIdx.x & 7, loc = blockIdx.x >> 3;
-    return (int64_t)(loc / G) * (8 * G) + xcd * G + loc % G;
-}
-
 // the own-row operands of a lane (rows row, row + 1 of b, idiag, x) and the epilogue on them
 struct MgOwn { f64x2 b, d, x; };
 template <int MODE>
@@ -163,11 +153,11 @@ __global__ __launch_bounds__(256) void k_mg_sl(int32_t n, const uint32_t *__rest
     constexpr int BLOCK = 256;
     __shared__ int32_t dl[16];
     // flag, dictionary, the first slice's codes / values and the lane's own rows are all requested before any is waited for
-    const int st = flag ? *flag : 0;
+    const int st = stop_flag(flag);
     const int tid = threadIdx.x;
     const int32_t dv = tid < 16 ? dict[tid] : 0;
     const int64_t nsl = ((int64_t)n + kSlRows - 1) / kSlRows;
-    int64_t sl = mg_first_slice(remap);
+    int64_t sl = first_slice(remap);
     u32x2 cw = {0xffffffffu, 0xffffffffu};
     f64x2 v[W];
     MgOwn own;
@@ -187,19 +177,7 @@ __global__ __launch_bounds__(256) void k_mg_sl(int32_t n, const uint32_t *__rest
     while (have) {
         const int64_t nxt = sl + gridDim.x;
         const int32_t row = (int32_t)(sl * kSlRows) + 2 * tid;
-        double xa[W], xb[W];
-#pragma unroll
-        for (int u = 0; u < W; ++u) {
-            const uint32_t ca = (cw.x >> (4 * u)) & 15u, cb = (cw.y >> (4 * u)) & 15u;
-            xa[u] = ca != 15u ? x[row + dl[ca]] : 0.0;
-            xb[u] = cb != 15u ? x[row + 1 + dl[cb]] : 0.0;
-        }
-        f64x2 z = {0.0, 0.0};
-#pragma unroll
-        for (int u = 0; u < W; ++u) {
-            if (((cw.x >> (4 * u)) & 15u) != 15u) z.x = z.x + v[u].x * xa[u];
-            if (((cw.y >> (4 * u)) & 15u) != 15u) z.y = z.y + v[u].y * xb[u];
-        }
+        const f64x2 z = sl_row_sums<W>(f64x2{0.0, 0.0}, cw, v, x, row, dl);
         mg_store_own<MODE>(row, n, own, z, omega, out);
         sl = nxt;
         have = sl < nsl;
@@ -217,15 +195,13 @@ __global__ __launch_bounds__(256) void k_mg_slb(int32_t n, const uint8_t *__rest
                                                 const double *__restrict__ b, const double *__restrict__ idiag, double omega,
                                                 double *__restrict__ out, const int *__restrict__ flag, int remap)
 {
-    constexpr int BLOCK = 256;
-    constexpr int NCH = (W + 7) / 8;
     static_assert(W >= 9 && W <= 32, "rows of 9..32 entries");
     __shared__ int32_t dl[256];
-    const int st = flag ? *flag : 0;
+    const int st = stop_flag(flag);
     const int tid = threadIdx.x;
     const int32_t dv = dict[tid];
     const int64_t nsl = ((int64_t)n + kSlRows - 1) / kSlRows;
-    int64_t sl = mg_first_slice(remap);
+    int64_t sl = first_slice(remap);
     // the first slice's own rows travel with the flag and the dictionary
     MgOwn own;
     if (sl < nsl) own = mg_load_own<MODE>((int32_t)(sl * kSlRows) + 2 * tid, n, b, idiag, x);
@@ -235,39 +211,7 @@ __global__ __launch_bounds__(256) void k_mg_slb(int32_t n, const uint8_t *__rest
     while (sl < nsl) {
         const int64_t nxt = sl + gridDim.x;
         const int32_t row = (int32_t)(sl * kSlRows) + 2 * tid;
-        const f64x2 *vb = reinterpret_cast<const f64x2 *>(sval + sl * (int64_t)W * kSlRows) + tid;
-        const u32x4s *cb = reinterpret_cast<const u32x4s *>(sbcode + sl * (int64_t)(NCH * 8 * kSlRows)) + tid;      // 16 bytes: rows 2t, 2t+1
-        f64x2 z = {0.0, 0.0};
-        auto chunk = [&](int c, auto cnt_tag) {
-            constexpr int CNT = decltype(cnt_tag)::value;
-            f64x2 v[CNT];
-            double xa[CNT], xb[CNT];
-            const u32x4s cw = __builtin_nontemporal_load(cb + c * BLOCK);
-#pragma unroll
-            for (int u = 0; u < CNT; ++u) v[u] = __builtin_nontemporal_load(vb + (c * 8 + u) * BLOCK);
-#pragma unroll
-            for (int u = 0; u < CNT; ++u) {
-                const uint32_t ca = ((u < 4 ? cw.x : cw.y) >> (8 * (u & 3))) & 255u;
-                const uint32_t cbv = ((u < 4 ? cw.z : cw.w) >> (8 * (u & 3))) & 255u;
-                xa[u] = ca != 255u ? x[row + dl[ca]] : 0.0;
-                xb[u] = cbv != 255u ? x[row + 1 + dl[cbv]] : 0.0;
-            }
-#pragma unroll
-            for (int u = 0; u < CNT; ++u) {
-                const uint32_t ca = ((u < 4 ? cw.x : cw.y) >> (8 * (u & 3))) & 255u;
-                const uint32_t cbv = ((u < 4 ? cw.z : cw.w) >> (8 * (u & 3))) & 255u;
-                if (ca != 255u) z.x = z.x + v[u].x * xa[u];
-                if (cbv != 255u) z.y = z.y + v[u].y * xb[u];
-            }
-        };
-        if (W > 28) {       // (k_csr_slb: rolled beyond 28 slots)
-#pragma unroll 1
-            for (int c = 0; c < W / 8; ++c) chunk(c, std::integral_constant<int, 8>{});
-        } else {
-#pragma unroll
-            for (int c = 0; c < W / 8; ++c) chunk(c, std::integral_constant<int, 8>{});
-        }
-        if (W % 8) chunk(W / 8, std::integral_constant<int, (W % 8 ? W % 8 : 8)>{});
+        const f64x2 z = slb_row_sums<W>(f64x2{0.0, 0.0}, sval, sbcode, sl, tid, x, row, dl);
         mg_store_own<MODE>(row, n, own, z, omega, out);
         sl = nxt;
         if (sl < nsl) own = mg_load_own<MODE>((int32_t)(sl * kSlRows) + 2 * tid, n, b, idiag, x);
@@ -302,7 +246,7 @@ static void launch_fused(const Part &p, int path, const double *x, const double 
                          double *out, const int *flag)
 {
     const int grid = grid_for_rows(p, p.n > 0 ? p.n : 1, kMaxGrid, false);
-    const int remap = grid % 256 == 0 && (grid <= kMaxGrid / 2 || (int64_t)p.n < (int64_t)32768 * kSlRows) ? 1 : 0;
+    const int remap = slice_map_mode(grid, p.n);
     hipStream_t st = g_rt.stream;
     if (path == 1) {
 #define LV(WW)                                                                                                          \

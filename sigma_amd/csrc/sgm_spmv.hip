@@ -24,38 +24,16 @@
 //               per lane), products are parked in LDS, the owner adds them.          12 B / entry
 // The x gather is served by L2 (the workgroup -> row-block / slice maps keep neighbouring rows on one
 // XCD).  Algorithmic bytes per SpMV on the reference layout: 12*nnz + 4*(n+1) + 8*m + 8*n.
-#include "sgm_spmv_select.hpp"
+#include "sgm_spmv_device.hpp"
 #include "sgm_plan_host.hpp"
+
+#include <cassert>
 
 namespace sgm {
 
 // ---------------------------------------------------------------------------------
 // kernels
 // ---------------------------------------------------------------------------------
-
-
-
-// Work-group -> row-block map.  Blocks b and b+8 share an XCD (round-robin dispatch), so
-// the blocks of one XCD take CONSECUTIVE row blocks inside each sweep of the grid: the x
-// entries they gather (own rows +- the stencil reach) stay in that XCD's 4 MiB L2.
-// Bijective because the grid is a multiple of 8.  Placement only changes speed.
-__device__ inline int64_t rowblock_of(int it, int b, int grid, int64_t nrb = 0, int mode = 1)
-{
-    const int per = grid >> 3;
-    if (mode == 2) {        // XCD-major: every XCD walks its own contiguous eighth of the rows
-        const int64_t chunk = (nrb + 7) / 8;
-        const int64_t local = (int64_t)it * per + (b >> 3);
-        return local < chunk ? (int64_t)(b & 7) * chunk + local : nrb;
-    }
-    return (int64_t)it * grid + (int64_t)(b & 7) * per + (b >> 3);
-}
-
-
-template <class T>
-__device__ inline T ld_stream(const T *p, bool nt)
-{
-    return nt ? __builtin_nontemporal_load(p) : *p;
-}
 
 // BLOCK threads own BLOCK consecutive rows; TILE = 2*BLOCK*VPT products are staged per pass.
 template <int BLOCK, int VPT, bool NT, bool ADD, bool DOT_W, bool DOT_YY>
@@ -68,17 +46,16 @@ __global__ __launch_bounds__(BLOCK) void k_csr_spmv(
     constexpr int TILE = 2 * BLOCK * VPT;
     __shared__ double prod[TILE];
     __shared__ double red[BLOCK / 64];
-    if (flag_done) { const int st = *flag_done; if (st && gen >= st) return; }
+    if (stopped(flag_done, gen)) return;
 
     const int tid = threadIdx.x;
-    const bool chain = (remap & 256) != 0;      // launch flag bits above the XCD-map mode
-    const int rmode = remap & 255;
+    const bool chain = (remap & kChainBit) != 0;
     const int64_t nrb = ((int64_t)n + BLOCK - 1) / BLOCK;
     double dwy = 0.0, dyy = 0.0;
 
     for (int it = 0;; ++it) {
         if ((int64_t)it * gridDim.x >= nrb) break;
-        const int64_t rb = rmode ? rowblock_of(it, blockIdx.x, gridDim.x, nrb, rmode) : (int64_t)it * gridDim.x + blockIdx.x;
+        const int64_t rb = rowblock_of(it, blockIdx.x, gridDim.x);
         if (rb >= nrb) continue;          // uniform per block
         const int32_t r0 = (int32_t)(rb * BLOCK);
         const int32_t r1 = min(r0 + BLOCK, n);
@@ -93,7 +70,7 @@ __global__ __launch_bounds__(BLOCK) void k_csr_spmv(
         }
         const int32_t s = rowptr[r0] & ~1;    // tile starts are even: 16-B aligned val loads
         const int32_t e = rowptr[r1];
-        double z = (ADD && chain) ? y0 : 0.0;   // chain: the row sum continues from y(i) (transpose products)
+        double z = row_start<ADD>(y0, chain);
 
         for (int32_t ts = s; ts < e; ts += TILE) {
             const int32_t te = min(ts + TILE, e);
@@ -104,8 +81,8 @@ __global__ __launch_bounds__(BLOCK) void k_csr_spmv(
             for (int m = 0; m < VPT; ++m) {
                 const int32_t j = ts + 2 * tid + 2 * BLOCK * m;
                 if (j < te) {     // arrays are padded by 2 entries: j+1 is always readable
-                    v[m] = ld_stream(reinterpret_cast<const f64x2 *>(val + j), NT);
-                    c[m] = ld_stream(reinterpret_cast<const i32x2 *>(col + j), NT);
+                    v[m] = *reinterpret_cast<const f64x2 *>(val + j);      // (plain loads: NT covers the store of y)
+                    c[m] = *reinterpret_cast<const i32x2 *>(col + j);
                 }
             }
 #pragma unroll
@@ -164,20 +141,12 @@ __global__ __launch_bounds__(BLOCK) void k_csr_spmv(
             __syncthreads();
         }
         if (row < n) {
-            const double yi = ADD ? (chain ? z : y0 + z) : 0.0 + z;
+            const double yi = row_value<ADD>(y0, z, chain);
             if (NT) __builtin_nontemporal_store(yi, y + row); else y[row] = yi;
-            if (DOT_W) dwy += wv * yi;
-            if (DOT_YY) dyy += yi * yi;
+            dots_add<DOT_W, DOT_YY>(wv, yi, dwy, dyy);
         }
     }
-    if (DOT_W) {
-        const double t = block_sum<BLOCK>(dwy, red);
-        if (tid == 0) part_wy[blockIdx.x] = t;
-    }
-    if (DOT_YY) {
-        const double t = block_sum<BLOCK>(dyy, red);
-        if (tid == 0) part_yy[blockIdx.x] = t;
-    }
+    dots_write<BLOCK, DOT_W, DOT_YY>(dwy, dyy, red, part_wy, part_yy);
 }
 
 // General CSR with LONG rows (no dictionary, rows beyond the row-owner kernel's 64 entries: finite-element matrices of
@@ -211,16 +180,15 @@ __global__ __launch_bounds__(256, 3) void k_csr_rl(
     __shared__ int32_t rp[BLOCK + 1];
     __shared__ int wmax[BLOCK / 64];
     __shared__ double red[BLOCK / 64];
-    if (flag_done) { const int st = *flag_done; if (st && gen >= st) return; }
+    if (stopped(flag_done, gen)) return;
     const int tid = threadIdx.x;
-    const bool chain = (remap & 256) != 0;
-    const int rmode = remap & 255;
+    const bool chain = (remap & kChainBit) != 0;
     const int64_t nrb = ((int64_t)n + BLOCK - 1) / BLOCK;
     const int sj = tid >> 3, sp = 2 * (tid & 7);
     double dwy = 0.0, dyy = 0.0;
     for (int it = 0;; ++it) {
         if ((int64_t)it * gridDim.x >= nrb) break;
-        const int64_t rb = rmode ? rowblock_of(it, blockIdx.x, gridDim.x, nrb, rmode) : (int64_t)it * gridDim.x + blockIdx.x;
+        const int64_t rb = rowblock_of(it, blockIdx.x, gridDim.x);
         if (rb >= nrb) continue;
         const int32_t r0 = (int32_t)(rb * BLOCK);
         const int32_t row = r0 + tid;
@@ -259,7 +227,7 @@ __global__ __launch_bounds__(256, 3) void k_csr_rl(
                     cq[m] = __builtin_nontemporal_load(reinterpret_cast<const i32x4 *>(col + base4));
             }
         };
-        double z = (ADD && chain) ? y0 : 0.0;
+        double z = row_start<ADD>(y0, chain);
         if (npass > 0) fetch(0);
         for (int c = 0; c < npass; ++c) {
 #pragma unroll
@@ -299,14 +267,12 @@ __global__ __launch_bounds__(256, 3) void k_csr_rl(
             __syncthreads();
         }
         if (row < n) {
-            const double yi = ADD ? (chain ? z : y0 + z) : 0.0 + z;
+            const double yi = row_value<ADD>(y0, z, chain);
             __builtin_nontemporal_store(yi, y + row);
-            if (DOT_W) dwy += wv * yi;
-            if (DOT_YY) dyy += yi * yi;
+            dots_add<DOT_W, DOT_YY>(wv, yi, dwy, dyy);
         }
     }
-    if (DOT_W) { const double t = block_sum<BLOCK>(dwy, red); if (tid == 0) part_wy[blockIdx.x] = t; }
-    if (DOT_YY) { const double t = block_sum<BLOCK>(dyy, red); if (tid == 0) part_yy[blockIdx.x] = t; }
+    dots_write<BLOCK, DOT_W, DOT_YY>(dwy, dyy, red, part_wy, part_yy);
 }
 
 // CSR with dictionary-coded column offsets ("offset-dict" form).  Matrices from structured
@@ -339,12 +305,11 @@ __global__ __launch_bounds__(BLOCK) void k_csr_do(
     __shared__ uint32_t cl4[TILE * CW / 4];
     __shared__ int32_t dl[CW == 1 ? 256 : 1];
     __shared__ double red[BLOCK / 64];
-    if (flag_done) { const int st = *flag_done; if (st && gen >= st) return; }
+    if (stopped(flag_done, gen)) return;
     const uint8_t *cl = reinterpret_cast<const uint8_t *>(cl4);
 
     const int tid = threadIdx.x;
-    const bool chain = (remap & 256) != 0;      // launch flag bits above the XCD-map mode
-    const int rmode = remap & 255;
+    const bool chain = (remap & kChainBit) != 0;
     if (CW == 1)
         for (int t = tid; t < 256; t += BLOCK) dl[t] = dict[t];
     const int32_t *col32 = reinterpret_cast<const int32_t *>(code);
@@ -353,7 +318,7 @@ __global__ __launch_bounds__(BLOCK) void k_csr_do(
 
     for (int it = 0;; ++it) {
         if ((int64_t)it * gridDim.x >= nrb) break;
-        const int64_t rb = rmode ? rowblock_of(it, blockIdx.x, gridDim.x, nrb, rmode) : (int64_t)it * gridDim.x + blockIdx.x;
+        const int64_t rb = rowblock_of(it, blockIdx.x, gridDim.x);
         if (rb >= nrb) continue;
         const int32_t r0 = (int32_t)(rb * BLOCK);
         const int32_t r1 = min(r0 + BLOCK, n);
@@ -367,7 +332,7 @@ __global__ __launch_bounds__(BLOCK) void k_csr_do(
         }
         const int32_t s = rowptr[r0] & ~3;    // tiles start at multiples of 4 entries: aligned 4-B code loads
         const int32_t e = rowptr[r1];
-        double z = (ADD && chain) ? y0 : 0.0;   // chain: the row sum continues from y(i) (transpose products)
+        double z = row_start<ADD>(y0, chain);
 
         // int32 columns on the largest tiles (long rows: several tiles per row block, phase 2 walks for microseconds): the
         // next tile's loads are requested before this tile is walked (24 more registers; the short-row shapes that must
@@ -442,23 +407,15 @@ __global__ __launch_bounds__(BLOCK) void k_csr_do(
             }
         }
         if (row < n) {
-            const double yi = ADD ? (chain ? z : y0 + z) : 0.0 + z;
+            const double yi = row_value<ADD>(y0, z, chain);
             __builtin_nontemporal_store(yi, y + row);
             // w(row) is read here, not with the row pointers: held across the row sum it costs the two
             // registers that push the fused variants over 64 VGPRs (7 instead of 8 waves per SIMD, and
             // a persistent grid sized for 8 then runs a second round); w is x or was just gathered: an L2 hit
-            if (DOT_W) dwy += w[row] * yi;
-            if (DOT_YY) dyy += yi * yi;
+            dots_add<DOT_W, DOT_YY>(DOT_W ? w[row] : 0.0, yi, dwy, dyy);
         }
     }
-    if (DOT_W) {
-        const double t = block_sum<BLOCK>(dwy, red);
-        if (tid == 0) part_wy[blockIdx.x] = t;
-    }
-    if (DOT_YY) {
-        const double t = block_sum<BLOCK>(dyy, red);
-        if (tid == 0) part_yy[blockIdx.x] = t;
-    }
+    dots_write<BLOCK, DOT_W, DOT_YY>(dwy, dyy, red, part_wy, part_yy);
 }
 
 // Sliced form of the offset-dict kernel, for matrices whose rows hold <= 8 entries drawn from
@@ -486,24 +443,15 @@ __global__ __launch_bounds__(256) void k_csr_sl(
     // The stop flag, the offset dictionary and the first slice's code words and values are all REQUESTED before any of them
     // is waited for (the flag is looked at before the first store): one memory round trip where flag -> dictionary -> slice
     // would be three -- which is what a product on a small matrix (a slice or two per workgroup) consists of.
-    const int st = flag_done ? *flag_done : 0;
+    const int st = stop_flag(flag_done);
     const int tid = threadIdx.x;
-    const bool chain = (remap & 256) != 0;
+    const bool chain = (remap & kChainBit) != 0;
     const int32_t dv = tid < 16 ? dict[tid] : 0;
     const int64_t nsl = ((int64_t)n + kSlRows - 1) / kSlRows;
     double dwy = 0.0, dyy = 0.0;
 
-    // block map: round-robin, or XCD-block-cyclic (remap mode 3/4/5 = groups of G = 8/2/32): inside every
-    // window of 8 G consecutive slices the workgroups of one XCD (blockIdx % 8) take G consecutive
-    // slices, so the x entries a slice shares with its neighbours (2-D stencils: +-nx rows = a few
-    // slices away) are fetched into ONE XCD's L2 instead of several (C2: 103.8 -> 99-100 us).  The
-    // launcher only asks for it when the grid is a multiple of 8 G (the map is then a permutation).
-    int64_t first = blockIdx.x;
-    if ((remap & 255) >= 3) {
-        const int G = (remap & 255) == 3 ? 8 : (remap & 255) == 4 ? 2 : (remap & 255) == 6 ? 64 : (remap & 255) == 7 ? 128 : 32;
-        const int xcd = blockIdx.x & 7, loc = blockIdx.x >> 3;
-        first = (int64_t)(loc / G) * (8 * G) + xcd * G + loc % G;
-    }
+    // block map: round-robin or XCD-block-cyclic (first_slice)
+    const int64_t first = first_slice(remap & kSliceMapBits);
     // ... or a slice schedule (slice_sched below; matrices with a far offset, 3-D grids): entry it * grid + workgroup of
     // a table, -1 = nothing left; the next entry is requested (a scalar load) before this slice's work
     int64_t sl = sched ? sched[blockIdx.x] : first;
@@ -520,57 +468,21 @@ __global__ __launch_bounds__(256) void k_csr_sl(
     };
     bool have = sl >= 0 && sl < nsl;
     if (have) load_slice(sl);
-    if (st && gen >= st) return;
+    if (stop_hit(st, gen)) return;
     if (tid < 16) dl[tid] = dv;
     __syncthreads();
     while (have) {
         int64_t nxt = sl + gridDim.x;
         if (sched) { ++sit; nxt = sit < sched_iters ? sched[(int64_t)sit * gridDim.x + blockIdx.x] : -1; }
         const int32_t row = (int32_t)(sl * kSlRows) + 2 * tid;
-        f64x2 y0 = {0.0, 0.0};
-        if (ADD) {
-            if (row + 1 < n) y0 = *reinterpret_cast<const f64x2 *>(y + row);
-            else if (row < n) y0.x = y[row];
-        }
-        double xa[W], xb[W];
-#pragma unroll
-        for (int u = 0; u < W; ++u) {
-            const uint32_t ca = (cw.x >> (4 * u)) & 15u, cb = (cw.y >> (4 * u)) & 15u;
-            xa[u] = ca != 15u ? x[row + dl[ca]] : 0.0;
-            xb[u] = cb != 15u ? x[row + 1 + dl[cb]] : 0.0;
-        }
-        f64x2 z;
-        z.x = (ADD && chain) ? y0.x : 0.0;
-        z.y = (ADD && chain) ? y0.y : 0.0;
-#pragma unroll
-        for (int u = 0; u < W; ++u) {
-            if (((cw.x >> (4 * u)) & 15u) != 15u) z.x = z.x + v[u].x * xa[u];
-            if (((cw.y >> (4 * u)) & 15u) != 15u) z.y = z.y + v[u].y * xb[u];
-        }
-        f64x2 yi;
-        yi.x = ADD ? (chain ? z.x : y0.x + z.x) : 0.0 + z.x;
-        yi.y = ADD ? (chain ? z.y : y0.y + z.y) : 0.0 + z.y;
-        if (row + 1 < n) {
-            __builtin_nontemporal_store(yi, reinterpret_cast<f64x2 *>(y + row));
-            if (DOT_W) { const f64x2 wv = *reinterpret_cast<const f64x2 *>(w + row); dwy += wv.x * yi.x; dwy += wv.y * yi.y; }
-            if (DOT_YY) { dyy += yi.x * yi.x; dyy += yi.y * yi.y; }
-        } else if (row < n) {
-            __builtin_nontemporal_store(yi.x, y + row);
-            if (DOT_W) dwy += w[row] * yi.x;
-            if (DOT_YY) dyy += yi.x * yi.x;
-        }
+        const f64x2 y0 = pair_load_y0<ADD>(y, row, n);
+        const f64x2 z = sl_row_sums<W>(pair_start<ADD>(y0, chain), cw, v, x, row, dl);
+        pair_finish<ADD, DOT_W, DOT_YY>(y, w, row, n, y0, z, chain, dwy, dyy);
         sl = nxt;
         have = sl >= 0 && sl < nsl;
         if (have) load_slice(sl);
     }
-    if (DOT_W) {
-        const double t = block_sum<BLOCK>(dwy, red);
-        if (tid == 0) part_wy[blockIdx.x] = t;
-    }
-    if (DOT_YY) {
-        const double t = block_sum<BLOCK>(dyy, red);
-        if (tid == 0) part_yy[blockIdx.x] = t;
-    }
+    dots_write<BLOCK, DOT_W, DOT_YY>(dwy, dyy, red, part_wy, part_yy);
 }
 
 // SELL-128-512: general matrices whose rows are too long (> 32 entries) or too uneven for one slice width.
@@ -600,15 +512,19 @@ __global__ __launch_bounds__(256 * GS) void k_csr_sell(
     constexpr int BLOCK = 256 * GS;
     extern __shared__ double xs[];               // XW: the window of x of the workgroup's slice(s)
     __shared__ double red[BLOCK / 64];
-    const int st = flag_done ? *flag_done : 0;
+    const int st = stop_flag(flag_done);
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const bool chain = (remap & 256) != 0;
+    const bool chain = (remap & kChainBit) != 0;
     const int64_t nsl = ((int64_t)n + kSlRows - 1) / kSlRows;
     double dwy = 0.0, dyy = 0.0;
-    if (st && gen >= st) return;
+    if (stop_hit(st, gen)) return;
 
-    int64_t first = blockIdx.x;             // XCD-block-cyclic slices, see k_csr_sl
+    // The slice map keeps its earlier inline text and numbering here (mode 5 = first_slice's XCD-block-cyclic map with
+    // G = 32, the only one launch_csr_sell passes besides 0; 3 / 4 / 6 / 7 = G 8 / 2 / 64 / 128 are not launched).  With
+    // first_slice() in its place the x-window kernel measured 12 % slower on rows of 20..40 entries although its slice loop
+    // was instruction-identical (profiles/spmv_dedupe/README.md); this text compiles to the kernels that were measured.
+    int64_t first = blockIdx.x;
     if ((remap & 255) >= 3) {
         const int G = (remap & 255) == 3 ? 8 : (remap & 255) == 4 ? 2 : (remap & 255) == 6 ? 64 : (remap & 255) == 7 ? 128 : 32;
         const int xcd = blockIdx.x & 7, loc = blockIdx.x >> 3;
@@ -640,7 +556,7 @@ __global__ __launch_bounds__(256 * GS) void k_csr_sell(
         if (ADD) { if (va) ya = y[ra]; if (vb_) yb = y[rb]; }
         const f64x2 *vb = reinterpret_cast<const f64x2 *>(sval + o0) + lane;
         const i32x2 *cb = reinterpret_cast<const i32x2 *>(scol + o0) + lane;
-        double za = (ADD && chain) ? ya : 0.0, zb = (ADD && chain) ? yb : 0.0;
+        double za = row_start<ADD>(ya, chain), zb = row_start<ADD>(yb, chain);
         auto slots = [&](int32_t c0, auto CHc) {
             constexpr int CH = decltype(CHc)::value;
             f64x2 v[CH];
@@ -666,27 +582,17 @@ __global__ __launch_bounds__(256 * GS) void k_csr_sell(
         for (; c0 + 8 <= W; c0 += 8) slots(c0, std::integral_constant<int, 8>());
         if (c0 + 4 <= W) { slots(c0, std::integral_constant<int, 4>()); c0 += 4; }
         if (c0 < W) slots(c0, std::integral_constant<int, 2>());
-        const double yia = ADD ? (chain ? za : ya + za) : 0.0 + za;
-        const double yib = ADD ? (chain ? zb : yb + zb) : 0.0 + zb;
+        const double yia = row_value<ADD>(ya, za, chain), yib = row_value<ADD>(yb, zb, chain);
         if (va) {
             y[ra] = yia;
-            if (DOT_W) dwy += w[ra] * yia;
-            if (DOT_YY) dyy += yia * yia;
+            dots_add<DOT_W, DOT_YY>(DOT_W ? w[ra] : 0.0, yia, dwy, dyy);
         }
         if (vb_) {
             y[rb] = yib;
-            if (DOT_W) dwy += w[rb] * yib;
-            if (DOT_YY) dyy += yib * yib;
+            dots_add<DOT_W, DOT_YY>(DOT_W ? w[rb] : 0.0, yib, dwy, dyy);
         }
     }
-    if (DOT_W) {
-        const double t = block_sum<BLOCK>(dwy, red);
-        if (threadIdx.x == 0) part_wy[blockIdx.x] = t;
-    }
-    if (DOT_YY) {
-        const double t = block_sum<BLOCK>(dyy, red);
-        if (threadIdx.x == 0) part_yy[blockIdx.x] = t;
-    }
+    dots_write<BLOCK, DOT_W, DOT_YY>(dwy, dyy, red, part_wy, part_yy);
 }
 
 // The sliced form for matrices WITHOUT an offset dictionary (arbitrary columns) whose rows are short
@@ -702,30 +608,19 @@ __global__ __launch_bounds__(256) void k_csr_sl32(
 {
     constexpr int BLOCK = 256;
     __shared__ double red[BLOCK / 64];
-    if (flag_done) { const int st = *flag_done; if (st && gen >= st) return; }
+    if (stopped(flag_done, gen)) return;
     const int tid = threadIdx.x;
-    const bool chain = (remap & 256) != 0;
+    const bool chain = (remap & kChainBit) != 0;
     const int64_t nsl = ((int64_t)n + kSlRows - 1) / kSlRows;
     double dwy = 0.0, dyy = 0.0;
 
-    int64_t first = blockIdx.x;             // XCD-block-cyclic slices, see k_csr_sl
-    if ((remap & 255) >= 3) {
-        const int G = (remap & 255) == 3 ? 8 : (remap & 255) == 4 ? 2 : (remap & 255) == 6 ? 64 : (remap & 255) == 7 ? 128 : 32;
-        const int xcd = blockIdx.x & 7, loc = blockIdx.x >> 3;
-        first = (int64_t)(loc / G) * (8 * G) + xcd * G + loc % G;
-    }
+    const int64_t first = first_slice(remap & kSliceMapBits);
     for (int64_t sl = first; sl < nsl; sl += gridDim.x) {
         const int32_t row = (int32_t)(sl * kSlRows) + 2 * tid;
         const f64x2 *vb = reinterpret_cast<const f64x2 *>(sval + sl * (int64_t)(W * kSlRows)) + tid;
         const i32x2 *cb = reinterpret_cast<const i32x2 *>(scol + sl * (int64_t)(W * kSlRows)) + tid;
-        f64x2 y0 = {0.0, 0.0};
-        if (ADD) {
-            if (row + 1 < n) y0 = *reinterpret_cast<const f64x2 *>(y + row);
-            else if (row < n) y0.x = y[row];
-        }
-        f64x2 z;
-        z.x = (ADD && chain) ? y0.x : 0.0;
-        z.y = (ADD && chain) ? y0.y : 0.0;
+        const f64x2 y0 = pair_load_y0<ADD>(y, row, n);
+        f64x2 z = pair_start<ADD>(y0, chain);
 #pragma unroll
         for (int c0 = 0; c0 < W; c0 += 8) {
             constexpr int CH = 8;
@@ -752,27 +647,9 @@ __global__ __launch_bounds__(256) void k_csr_sl32(
                 }
             if (W > 8) __builtin_amdgcn_sched_barrier(0);       // one chunk's registers at a time (all chunks at once, W = 28: 256 VGPRs, 302 -> 320 us)
         }
-        f64x2 yi;
-        yi.x = ADD ? (chain ? z.x : y0.x + z.x) : 0.0 + z.x;
-        yi.y = ADD ? (chain ? z.y : y0.y + z.y) : 0.0 + z.y;
-        if (row + 1 < n) {
-            __builtin_nontemporal_store(yi, reinterpret_cast<f64x2 *>(y + row));
-            if (DOT_W) { const f64x2 wv = *reinterpret_cast<const f64x2 *>(w + row); dwy += wv.x * yi.x; dwy += wv.y * yi.y; }
-            if (DOT_YY) { dyy += yi.x * yi.x; dyy += yi.y * yi.y; }
-        } else if (row < n) {
-            __builtin_nontemporal_store(yi.x, y + row);
-            if (DOT_W) dwy += w[row] * yi.x;
-            if (DOT_YY) dyy += yi.x * yi.x;
-        }
+        pair_finish<ADD, DOT_W, DOT_YY>(y, w, row, n, y0, z, chain, dwy, dyy);
     }
-    if (DOT_W) {
-        const double t = block_sum<BLOCK>(dwy, red);
-        if (tid == 0) part_wy[blockIdx.x] = t;
-    }
-    if (DOT_YY) {
-        const double t = block_sum<BLOCK>(dyy, red);
-        if (tid == 0) part_yy[blockIdx.x] = t;
-    }
+    dots_write<BLOCK, DOT_W, DOT_YY>(dwy, dyy, red, part_wy, part_yy);
 }
 
 // The sliced form for rows of 9..32 entries drawn from <= 255 distinct (column - row) offsets (27- / 19-point stencils,
@@ -791,104 +668,36 @@ __global__ __launch_bounds__(256) void k_csr_slb(
     const int32_t *__restrict__ sched, int sched_iters)
 {
     constexpr int BLOCK = 256;
-    constexpr int NCH = (W + 7) / 8;
     static_assert(W >= 9 && W <= 32, "rows of 9..32 entries");
     __shared__ int32_t dl[256];
     __shared__ double red[BLOCK / 64];
-    if (flag_done) { const int st = *flag_done; if (st && gen >= st) return; }
+    if (stopped(flag_done, gen)) return;
     const int tid = threadIdx.x;
     dl[tid] = dict[tid];
     __syncthreads();
-    const bool chain = (remap & 256) != 0;
+    const bool chain = (remap & kChainBit) != 0;
     const int64_t nsl = ((int64_t)n + kSlRows - 1) / kSlRows;
     double dwy = 0.0, dyy = 0.0;
 
-    int64_t first = blockIdx.x;             // XCD-block-cyclic slices, see k_csr_sl
-    if ((remap & 255) >= 3) {
-        const int G = (remap & 255) == 3 ? 8 : (remap & 255) == 4 ? 2 : (remap & 255) == 6 ? 64 : (remap & 255) == 7 ? 128 : 32;
-        const int xcd = blockIdx.x & 7, loc = blockIdx.x >> 3;
-        first = (int64_t)(loc / G) * (8 * G) + xcd * G + loc % G;
-    }
+    const int64_t first = first_slice(remap & kSliceMapBits);
     int64_t sl = sched ? sched[blockIdx.x] : first;        // slice schedule, see k_csr_sl
     int sit = 0;
     while (sl >= 0 && sl < nsl) {
         int64_t nxt = sl + gridDim.x;
         if (sched) { ++sit; nxt = sit < sched_iters ? sched[(int64_t)sit * gridDim.x + blockIdx.x] : -1; }
         const int32_t row = (int32_t)(sl * kSlRows) + 2 * tid;
-        const f64x2 *vb = reinterpret_cast<const f64x2 *>(sval + sl * (int64_t)W * kSlRows) + tid;
-        const u32x4s *cb = reinterpret_cast<const u32x4s *>(sbcode + sl * (int64_t)(NCH * 8 * kSlRows)) + tid;      // 16 bytes: rows 2t, 2t+1
-        f64x2 y0 = {0.0, 0.0};
-        if (ADD) {
-            if (row + 1 < n) y0 = *reinterpret_cast<const f64x2 *>(y + row);
-            else if (row < n) y0.x = y[row];
-        }
-        f64x2 z;
-        z.x = (ADD && chain) ? y0.x : 0.0;
-        z.y = (ADD && chain) ? y0.y : 0.0;
-        // chunks of 8 slots.  Unrolled over all chunks the compiler keeps every slot live (237 VGPRs at W = 27, two waves
-        // per SIMD) -- which still wins up to W = 28: all of a wave's loads are in flight at once; beyond that a rolled loop
-        auto chunk = [&](int c, auto cnt_tag) {
-            constexpr int CNT = decltype(cnt_tag)::value;
-            f64x2 v[CNT];
-            double xa[CNT], xb[CNT];
-            const u32x4s cw = __builtin_nontemporal_load(cb + c * BLOCK);
-#pragma unroll
-            for (int u = 0; u < CNT; ++u) v[u] = __builtin_nontemporal_load(vb + (c * 8 + u) * BLOCK);
-#pragma unroll
-            for (int u = 0; u < CNT; ++u) {
-                const uint32_t ca = ((u < 4 ? cw.x : cw.y) >> (8 * (u & 3))) & 255u;
-                const uint32_t cbv = ((u < 4 ? cw.z : cw.w) >> (8 * (u & 3))) & 255u;
-                xa[u] = ca != 255u ? x[row + dl[ca]] : 0.0;
-                xb[u] = cbv != 255u ? x[row + 1 + dl[cbv]] : 0.0;
-            }
-#pragma unroll
-            for (int u = 0; u < CNT; ++u) {
-                const uint32_t ca = ((u < 4 ? cw.x : cw.y) >> (8 * (u & 3))) & 255u;
-                const uint32_t cbv = ((u < 4 ? cw.z : cw.w) >> (8 * (u & 3))) & 255u;
-                if (ca != 255u) z.x = z.x + v[u].x * xa[u];
-                if (cbv != 255u) z.y = z.y + v[u].y * xb[u];
-            }
-        };
-        if (W > 28) {       // (measured on the 160^3 27-point matrix, rolled vs unrolled: W = 32: 249 vs 281 us; 28: 237 vs 224; 27: 229 vs 218)
-#pragma unroll 1
-            for (int c = 0; c < W / 8; ++c) chunk(c, std::integral_constant<int, 8>{});
-        } else {
-#pragma unroll
-            for (int c = 0; c < W / 8; ++c) chunk(c, std::integral_constant<int, 8>{});
-        }
-        if (W % 8) chunk(W / 8, std::integral_constant<int, (W % 8 ? W % 8 : 8)>{});
-        f64x2 yi;
-        yi.x = ADD ? (chain ? z.x : y0.x + z.x) : 0.0 + z.x;
-        yi.y = ADD ? (chain ? z.y : y0.y + z.y) : 0.0 + z.y;
-        if (row + 1 < n) {
-            __builtin_nontemporal_store(yi, reinterpret_cast<f64x2 *>(y + row));
-            if (DOT_W) { const f64x2 wv = *reinterpret_cast<const f64x2 *>(w + row); dwy += wv.x * yi.x; dwy += wv.y * yi.y; }
-            if (DOT_YY) { dyy += yi.x * yi.x; dyy += yi.y * yi.y; }
-        } else if (row < n) {
-            __builtin_nontemporal_store(yi.x, y + row);
-            if (DOT_W) dwy += w[row] * yi.x;
-            if (DOT_YY) dyy += yi.x * yi.x;
-        }
+        const f64x2 y0 = pair_load_y0<ADD>(y, row, n);
+        const f64x2 z = slb_row_sums<W>(pair_start<ADD>(y0, chain), sval, sbcode, sl, tid, x, row, dl);
+        pair_finish<ADD, DOT_W, DOT_YY>(y, w, row, n, y0, z, chain, dwy, dyy);
         sl = nxt;
     }
-    if (DOT_W) {
-        const double t = block_sum<BLOCK>(dwy, red);
-        if (tid == 0) part_wy[blockIdx.x] = t;
-    }
-    if (DOT_YY) {
-        const double t = block_sum<BLOCK>(dyy, red);
-        if (tid == 0) part_yy[blockIdx.x] = t;
-    }
+    dots_write<BLOCK, DOT_W, DOT_YY>(dwy, dyy, red, part_wy, part_yy);
 }
-
-
-
-
 
 // ELLPACK, slot-major device layout: lane i owns row i and walks ALL max_d slots in
 // order (padding slots multiply 0.0 by x(last neighbour), exactly like the reference,
 // so a non-finite x entry propagates the same way).
-template <int U, bool NT, bool ADD, bool DOT_W, bool DOT_YY>
+template <int U, bool NT /* unused: the loads are plain; kept in the kernel's name */, bool ADD, bool DOT_W, bool DOT_YY>
 __global__ __launch_bounds__(kBlock) void k_ell_spmv(
     int32_t n, int32_t max_d, const int32_t *__restrict__ ecol, const double *__restrict__ eval,
     const double *__restrict__ x, double *__restrict__ y, const double *__restrict__ w,
@@ -896,22 +705,22 @@ __global__ __launch_bounds__(kBlock) void k_ell_spmv(
     int chain)
 {
     __shared__ double red[kBlock / 64];
-    if (flag_done) { const int st = *flag_done; if (st && gen >= st) return; }
+    if (stopped(flag_done, gen)) return;
     double dwy = 0.0, dyy = 0.0;
     const int64_t stride = (int64_t)gridDim.x * kBlock;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
         double wv = 0.0, y0 = 0.0;
         if (DOT_W) wv = w[i];
         if (ADD) y0 = y[i];
-        double z = (ADD && chain) ? y0 : 0.0;
+        double z = row_start<ADD>(y0, chain);
         int32_t k = 0;
         for (; k + U <= max_d; k += U) {
             int32_t c[U];
             double v[U], xv[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                c[u] = ld_stream(ecol + (int64_t)(k + u) * n + i, NT);
-                v[u] = ld_stream(eval + (int64_t)(k + u) * n + i, NT);
+                c[u] = ecol[(int64_t)(k + u) * n + i];
+                v[u] = eval[(int64_t)(k + u) * n + i];
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) xv[u] = x[c[u]];
@@ -919,19 +728,11 @@ __global__ __launch_bounds__(kBlock) void k_ell_spmv(
             for (int u = 0; u < U; ++u) z = z + v[u] * xv[u];
         }
         for (; k < max_d; ++k) z = z + eval[(int64_t)k * n + i] * x[ecol[(int64_t)k * n + i]];
-        const double yi = ADD ? (chain ? z : y0 + z) : 0.0 + z;
+        const double yi = row_value<ADD>(y0, z, chain);
         y[i] = yi;
-        if (DOT_W) dwy += wv * yi;
-        if (DOT_YY) dyy += yi * yi;
+        dots_add<DOT_W, DOT_YY>(wv, yi, dwy, dyy);
     }
-    if (DOT_W) {
-        const double t = block_sum<kBlock>(dwy, red);
-        if (threadIdx.x == 0) part_wy[blockIdx.x] = t;
-    }
-    if (DOT_YY) {
-        const double t = block_sum<kBlock>(dyy, red);
-        if (threadIdx.x == 0) part_yy[blockIdx.x] = t;
-    }
+    dots_write<kBlock, DOT_W, DOT_YY>(dwy, dyy, red, part_wy, part_yy);
 }
 
 // ELLPACK with dictionary-coded column offsets (max_d <= 16, <= 255 distinct col-row offsets):
@@ -948,7 +749,7 @@ __global__ __launch_bounds__(kBlock) void k_ell_do(
 {
     __shared__ double red[kBlock / 64];
     __shared__ int32_t dl[256];
-    if (flag_done) { const int st = *flag_done; if (st && gen >= st) return; }
+    if (stopped(flag_done, gen)) return;
     for (int t = threadIdx.x; t < 256; t += kBlock) dl[t] = dict[t];
     __syncthreads();
     double dwy = 0.0, dyy = 0.0;
@@ -968,23 +769,15 @@ __global__ __launch_bounds__(kBlock) void k_ell_do(
                 v[k] = __builtin_nontemporal_load(eval + (int64_t)k * n + i);
                 xv[k] = x[i + dl[(cw[k >> 2] >> (8 * (k & 3))) & 255]];
             }
-        double z = (ADD && chain) ? y0 : 0.0;
+        double z = row_start<ADD>(y0, chain);
 #pragma unroll
         for (int k = 0; k < MDP; ++k)
             if (k < max_d) z = z + v[k] * xv[k];
-        const double yi = ADD ? (chain ? z : y0 + z) : 0.0 + z;
+        const double yi = row_value<ADD>(y0, z, chain);
         y[i] = yi;
-        if (DOT_W) dwy += wv * yi;
-        if (DOT_YY) dyy += yi * yi;
+        dots_add<DOT_W, DOT_YY>(wv, yi, dwy, dyy);
     }
-    if (DOT_W) {
-        const double t = block_sum<kBlock>(dwy, red);
-        if (threadIdx.x == 0) part_wy[blockIdx.x] = t;
-    }
-    if (DOT_YY) {
-        const double t = block_sum<kBlock>(dyy, red);
-        if (threadIdx.x == 0) part_yy[blockIdx.x] = t;
-    }
+    dots_write<kBlock, DOT_W, DOT_YY>(dwy, dyy, red, part_wy, part_yy);
 }
 
 __global__ void k_gather(double *__restrict__ dst, const double *__restrict__ src,
@@ -993,8 +786,6 @@ __global__ void k_gather(double *__restrict__ dst, const double *__restrict__ sr
     int32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t < count) dst[t] = src[idx[t]];
 }
-
-static int g_launch_flags = 0;        // 256: chained accumulation (see k_csr_* `chain`)
 
 int spmv_grid(const Part &p, bool whole)       // = number of partial sums one SpMV leaves per fused dot
 {
@@ -1014,209 +805,130 @@ int row_lines_resident_per_cu()
     return nb;
 }
 
-template <int BLOCK, int VPT, bool NT, bool ADD>
-static void launch_csr_cfg(const Part &p, int grid, const double *x, double *y, const double *w,
-                           double *pwy, double *pyy, const int *flag, int gen, int remap)
+// The launchers.  Each turns the run-time choices of a launch (SpmvArgs: add, fused dots) into the kernel's compile-time flags
+// through with_flags (F = the SpmvFlags type), and composes the kernel's `remap` argument from the slice-map mode and the chain bit.
+static int chain_bit(const SpmvArgs &a) { return a.chain ? kChainBit : 0; }
+
+static void launch_csr(const Part &p, int grid, const SpmvArgs &a)
 {
-    hipStream_t st = g_rt.stream;
-#define L(DW, DY)                                                                                  \
-    hipLaunchKernelGGL((k_csr_spmv<BLOCK, VPT, NT, ADD, DW, DY>), dim3(grid), dim3(BLOCK), 0, st,  \
-                       p.n, p.rowptr, p.col, p.val, x, y, w, pwy, pyy, flag, gen, remap)
-    if (w && pyy) L(true, true);
-    else if (w) L(true, false);
-    else if (pyy) L(false, true);
-    else L(false, false);
-#undef L
+    with_flags(a, [&](auto flags) {
+        using F = decltype(flags);
+        hipLaunchKernelGGL((k_csr_spmv<kSpmvBlock, kSpmvVpt, true, F::add, F::dot_w, F::dot_yy>), dim3(grid), dim3(kSpmvBlock), 0, g_rt.stream,
+                           p.n, p.rowptr, p.col, p.val, a.x, a.y, a.w, a.pwy, a.pyy, a.flag, a.gen, chain_bit(a));
+    });
 }
 
-template <bool ADD>
-static void launch_csr(const Part &p, int grid, const double *x, double *y, const double *w,
-                       double *pwy, double *pyy, const int *flag, int gen)
+static void launch_csr_rl(const Part &p, int grid, const SpmvArgs &a)
 {
-    const SpmvCfg &c = spmv_cfg();
-#define CFG(B, V)                                                                              \
-    if (c.block == B && c.vpt == V) {                                                          \
-        if (c.nt) launch_csr_cfg<B, V, true, ADD>(p, grid, x, y, w, pwy, pyy, flag, gen, c.remap | g_launch_flags);  \
-        else launch_csr_cfg<B, V, false, ADD>(p, grid, x, y, w, pwy, pyy, flag, gen, c.remap | g_launch_flags);      \
-        return;                                                                                \
-    }
-    CFG(256, 2) CFG(256, 4) CFG(256, 8) CFG(512, 2) CFG(512, 4) CFG(512, 8) CFG(1024, 2) CFG(1024, 4)
-#undef CFG
-    launch_csr_cfg<256, 2, true, ADD>(p, grid, x, y, w, pwy, pyy, flag, gen, c.remap | g_launch_flags);
+    with_flags(a, [&](auto flags) {
+        using F = decltype(flags);
+        hipLaunchKernelGGL((k_csr_rl<F::add, F::dot_w, F::dot_yy>), dim3(grid), dim3(256), 0, g_rt.stream, p.n, p.rowptr, p.col, p.val, a.x, a.y,
+                           a.w, a.pwy, a.pyy, a.flag, a.gen, chain_bit(a));
+    });
 }
 
-template <bool ADD>
-static void launch_csr_rl(const Part &p, int grid, const double *x, double *y, const double *w,
-                          double *pwy, double *pyy, const int *flag, int gen)
+static void launch_csr_do(const Part &p, int grid, const SpmvArgs &a)
 {
-    hipStream_t st = g_rt.stream;
-    const int remap = (spmv_cfg().remap == 2 ? 2 : 1) | g_launch_flags;
-#define L(DW, DY)                                                                                       \
-    hipLaunchKernelGGL((k_csr_rl<ADD, DW, DY>), dim3(grid), dim3(256), 0, st, p.n, p.rowptr, p.col, p.val, x, y, w, \
-                       pwy, pyy, flag, gen, remap)
-    if (w && pyy) L(true, true);
-    else if (w) L(true, false);
-    else if (pyy) L(false, true);
-    else L(false, false);
-#undef L
-}
-
-template <bool ADD>
-static void launch_csr_do(const Part &p, int grid, const double *x, double *y, const double *w,
-                          double *pwy, double *pyy, const int *flag, int gen)
-{
-    const SpmvCfg &c = spmv_cfg();
-    hipStream_t st = g_rt.stream;
     const int tile = do_tile_for(p);
     const bool dict = use_offset_dict(p);
-#define L(B, T, DW, DY)                                                                                 \
-    do {                                                                                                \
-        if (dict)                                                                                       \
-            hipLaunchKernelGGL((k_csr_do<B, T, 1, ADD, DW, DY>), dim3(grid), dim3(B), 0, st, p.n, p.rowptr, \
-                               p.code, p.dict, p.val, x, y, w, pwy, pyy, flag, gen, c.remap | g_launch_flags); \
-        else                                                                                            \
-            hipLaunchKernelGGL((k_csr_do<B, T, 4, ADD, DW, DY>), dim3(grid), dim3(B), 0, st, p.n, p.rowptr, \
-                               reinterpret_cast<const uint8_t *>(p.col), p.dict, p.val, x, y, w, pwy, pyy, flag, \
-                               gen, c.remap | g_launch_flags);                                          \
+    // do_tile_for gives the 1-byte-code form no tile beyond kDoMaxCodeTile: larger ones are not instantiated for it, and a
+    // launcher that found none would leave y unwritten
+    assert(!dict || tile <= kDoMaxCodeTile);
+    with_flags(a, [&](auto flags) {
+        using F = decltype(flags);
+#define LV(T)                                                                                                               \
+    if (tile == T) {                                                                                                        \
+        if (!dict)                                                                                                          \
+            hipLaunchKernelGGL((k_csr_do<kSpmvBlock, T, 4, F::add, F::dot_w, F::dot_yy>), dim3(grid), dim3(kSpmvBlock), 0, g_rt.stream, p.n, \
+                               p.rowptr, reinterpret_cast<const uint8_t *>(p.col), p.dict, p.val, a.x, a.y, a.w, a.pwy, a.pyy, \
+                               a.flag, a.gen, chain_bit(a));                                                                \
+        else if constexpr (T <= kDoMaxCodeTile)                                                                             \
+            hipLaunchKernelGGL((k_csr_do<kSpmvBlock, T, 1, F::add, F::dot_w, F::dot_yy>), dim3(grid), dim3(kSpmvBlock), 0, g_rt.stream, p.n, \
+                               p.rowptr, p.code, p.dict, p.val, a.x, a.y, a.w, a.pwy, a.pyy, a.flag, a.gen, chain_bit(a));  \
+        return;                                                                                                             \
+    }
+        SGM_DO_TILES(LV)
+#undef LV
+    });
+}
+
+static void launch_csr_sl(const Part &p, int grid, const SpmvArgs &a)
+{
+    const int remap = slice_map_mode(grid, p.n) | chain_bit(a);
+    with_flags(a, [&](auto flags) {
+        using F = decltype(flags);
+#define LV(WW)                                                                                                              \
+    if (p.sw == WW) {                                                                                                       \
+        hipLaunchKernelGGL((k_csr_sl<WW, F::add, F::dot_w, F::dot_yy>), dim3(grid), dim3(256), 0, g_rt.stream, p.n, p.scode, p.dict, p.sval, \
+                           a.x, a.y, a.w, a.pwy, a.pyy, a.flag, a.gen, remap, p.run_sched, p.run_iters);                    \
+        return;                                                                                                             \
+    }
+        SGM_SL_WIDTHS(LV)
+#undef LV
+    });
+}
+
+static void launch_csr_sl32(const Part &p, int grid, const SpmvArgs &a)
+{
+    const int remap = slice_map_mode(grid, p.n) | chain_bit(a);
+    with_flags(a, [&](auto flags) {
+        using F = decltype(flags);
+#define LV(WW)                                                                                                              \
+    if (p.sw == WW) {                                                                                                       \
+        hipLaunchKernelGGL((k_csr_sl32<WW, F::add, F::dot_w, F::dot_yy>), dim3(grid), dim3(256), 0, g_rt.stream, p.n, p.scol, p.sval, a.x, a.y, \
+                           a.w, a.pwy, a.pyy, a.flag, a.gen, remap);                                                        \
+        return;                                                                                                             \
+    }
+        SGM_SL32_WIDTHS(LV)
+#undef LV
+    });
+}
+
+static void launch_csr_slb(const Part &p, int grid, const SpmvArgs &a)
+{
+    const int remap = slice_map_mode(grid, p.n) | chain_bit(a);
+    with_flags(a, [&](auto flags) {
+        using F = decltype(flags);
+#define LV(WW)                                                                                                              \
+    if (p.sw == WW) {                                                                                                       \
+        hipLaunchKernelGGL((k_csr_slb<WW, F::add, F::dot_w, F::dot_yy>), dim3(grid), dim3(256), 0, g_rt.stream, p.n, p.sbcode, p.dict, p.sval, \
+                           a.x, a.y, a.w, a.pwy, a.pyy, a.flag, a.gen, remap, p.run_sched, p.run_iters);                    \
+        return;                                                                                                             \
+    }
+        SGM_SLB_WIDTHS(LV)
+#undef LV
+    });
+}
+
+static void launch_csr_sell(const Part &p, int grid, const SpmvArgs &a)
+{
+    const int remap = (slice_map_mode(grid, p.n) ? 5 : 0) | chain_bit(a);      // (k_csr_sell's own mode numbering, see there)
+    const bool xwin = p.sl_win0 && p.opt.csr_xwindow;        // banded: the window of x of one (two) slice(s) through LDS
+    const size_t lds = xwin ? (size_t)p.sl_span * 8 : 0;
+    with_flags(a, [&](auto flags) {
+        using F = decltype(flags);
+#define LXG(GG)                                                                                                             \
+    do {                                                                                                                    \
+        static size_t attr = 0;                                                                                             \
+        if (attr < lds) { (void)hipFuncSetAttribute((const void *)k_csr_sell<F::add, F::dot_w, F::dot_yy, true, GG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = lds; } \
+        hipLaunchKernelGGL((k_csr_sell<F::add, F::dot_w, F::dot_yy, true, GG>), dim3(grid), dim3(256 * GG), lds, g_rt.stream, p.n,          \
+                           (const int64_t *)p.sl_off, (const uint16_t *)p.sl_perm, (const int32_t *)p.sl_col,               \
+                           (const double *)p.sl_val, a.x, a.y, a.w, a.pwy, a.pyy, a.flag, a.gen, remap,                     \
+                           (const int32_t *)p.sl_win0, p.sl_span, (int32_t)p.xlen());                                       \
     } while (0)
-#define LV(B, T)                                \
-    if (c.block == B && tile == T) {            \
-        if (w && pyy) L(B, T, true, true);      \
-        else if (w) L(B, T, true, false);       \
-        else if (pyy) L(B, T, false, true);     \
-        else L(B, T, false, false);             \
-        return;                                 \
-    }
-    SGM_DO_VARIANTS(LV)
-#undef LV
-#undef L
-}
-
-template <bool ADD>
-static void launch_csr_sl(const Part &p, int grid, const double *x, double *y, const double *w,
-                          double *pwy, double *pyy, const int *flag, int gen)
-{
-    const SpmvCfg &c = spmv_cfg();
-    hipStream_t st = g_rt.stream;
-    // XCD-block-cyclic slices (G = 32) below 32768 slices, plain round-robin on the 8192 grids above that
-    // (measured: 300^3 363 vs 358 us) and wherever the grid is not a multiple of 8 G; SGM_SPMV_CFG's
-    // remap field overrides (0 = round-robin, 3/4/5 = G 8/2/32)
-    int mode = c.remap == 1 ? ((grid <= kMaxGrid / 2 || (int64_t)p.n < (int64_t)32768 * kSlRows) ? 5 : 0) : (c.remap >= 3 ? c.remap : 0);
-    if (mode >= 3 && grid % (8 * (mode == 3 ? 8 : mode == 4 ? 2 : mode == 6 ? 64 : mode == 7 ? 128 : 32)) != 0) mode = 0;
-#define L(WW, DW, DY)                                                                                   \
-    hipLaunchKernelGGL((k_csr_sl<WW, ADD, DW, DY>), dim3(grid), dim3(256), 0, st, p.n, p.scode, p.dict, \
-                       p.sval, x, y, w, pwy, pyy, flag, gen, mode | g_launch_flags, p.run_sched, p.run_iters)
-#define LV(WW)                                \
-    if (p.sw == WW) {                         \
-        if (w && pyy) L(WW, true, true);      \
-        else if (w) L(WW, true, false);       \
-        else if (pyy) L(WW, false, true);     \
-        else L(WW, false, false);             \
-        return;                               \
-    }
-    SGM_SL_WIDTHS(LV)
-#undef LV
-#undef L
-}
-
-template <bool ADD>
-static void launch_csr_sl32(const Part &p, int grid, const double *x, double *y, const double *w,
-                            double *pwy, double *pyy, const int *flag, int gen)
-{
-    hipStream_t st = g_rt.stream;
-    const SpmvCfg &c = spmv_cfg();
-    int mode = c.remap == 1 ? ((grid <= kMaxGrid / 2 || (int64_t)p.n < (int64_t)32768 * kSlRows) ? 5 : 0) : (c.remap >= 3 ? c.remap : 0);
-    if (mode >= 3 && grid % (8 * (mode == 3 ? 8 : mode == 4 ? 2 : mode == 6 ? 64 : mode == 7 ? 128 : 32)) != 0) mode = 0;
-#define L(WW, DW, DY)                                                                                     \
-    hipLaunchKernelGGL((k_csr_sl32<WW, ADD, DW, DY>), dim3(grid), dim3(256), 0, st, p.n, p.scol, p.sval, x, y, \
-                       w, pwy, pyy, flag, gen, mode | g_launch_flags)
-#define LV(WW)                                \
-    if (p.sw == WW) {                         \
-        if (w && pyy) L(WW, true, true);      \
-        else if (w) L(WW, true, false);       \
-        else if (pyy) L(WW, false, true);     \
-        else L(WW, false, false);             \
-        return;                               \
-    }
-    SGM_SL32_WIDTHS(LV)
-#undef LV
-#undef L
-}
-
-template <bool ADD>
-static void launch_csr_sell(const Part &p, int grid, const double *x, double *y, const double *w,
-                            double *pwy, double *pyy, const int *flag, int gen)
-{
-    hipStream_t st = g_rt.stream;
-    const SpmvCfg &c = spmv_cfg();
-    int mode = c.remap == 1 ? ((grid <= kMaxGrid / 2 || (int64_t)p.n < (int64_t)32768 * kSlRows) ? 5 : 0) : (c.remap >= 3 ? c.remap : 0);
-    if (mode >= 3 && grid % (8 * (mode == 3 ? 8 : mode == 4 ? 2 : mode == 6 ? 64 : mode == 7 ? 128 : 32)) != 0) mode = 0;
-#define L(DW, DY)                                                                                                    \
-    hipLaunchKernelGGL((k_csr_sell<ADD, DW, DY>), dim3(grid), dim3(256), 0, st, p.n, (const int64_t *)p.sl_off,       \
-                       (const uint16_t *)p.sl_perm, (const int32_t *)p.sl_col, (const double *)p.sl_val, x, y, w, pwy, pyy, flag, \
-                       gen, mode | g_launch_flags)
-#define LXG(DW, DY, GG)                                                                                              \
-    do {                                                                                                             \
-        static size_t attr = 0;                                                                                      \
-        if (attr < lds) { (void)hipFuncSetAttribute((const void *)k_csr_sell<ADD, DW, DY, true, GG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = lds; } \
-        hipLaunchKernelGGL((k_csr_sell<ADD, DW, DY, true, GG>), dim3(grid), dim3(256 * GG), lds, st, p.n, (const int64_t *)p.sl_off, \
-                           (const uint16_t *)p.sl_perm, (const int32_t *)p.sl_col, (const double *)p.sl_val, x, y, w, pwy, pyy, flag, \
-                           gen, mode | g_launch_flags, (const int32_t *)p.sl_win0, p.sl_span, (int32_t)p.xlen());     \
-    } while (0)
-#define LX(DW, DY) do { if (p.sl_gs == 2) LXG(DW, DY, 2); else LXG(DW, DY, 1); } while (0)
-    if (p.sl_win0 && p.opt.csr_xwindow) {        // banded: the window of x of one (two) slice(s) through LDS
-        const size_t lds = (size_t)p.sl_span * 8;
-        if (w && pyy) LX(true, true);
-        else if (w) LX(true, false);
-        else if (pyy) LX(false, true);
-        else LX(false, false);
-        return;
-    }
-    if (w && pyy) L(true, true);
-    else if (w) L(true, false);
-    else if (pyy) L(false, true);
-    else L(false, false);
-#undef LX
+        if (xwin && p.sl_gs == 2) LXG(2);
+        else if (xwin) LXG(1);
+        else
+            hipLaunchKernelGGL((k_csr_sell<F::add, F::dot_w, F::dot_yy>), dim3(grid), dim3(256), 0, g_rt.stream, p.n, (const int64_t *)p.sl_off,
+                               (const uint16_t *)p.sl_perm, (const int32_t *)p.sl_col, (const double *)p.sl_val, a.x, a.y, a.w,
+                               a.pwy, a.pyy, a.flag, a.gen, remap);
 #undef LXG
-#undef L
+    });
 }
 
-template <bool ADD>
-static void launch_csr_slb(const Part &p, int grid, const double *x, double *y, const double *w,
-                           double *pwy, double *pyy, const int *flag, int gen)
-{
-    hipStream_t st = g_rt.stream;
-    const SpmvCfg &c = spmv_cfg();
-    int mode = c.remap == 1 ? ((grid <= kMaxGrid / 2 || (int64_t)p.n < (int64_t)32768 * kSlRows) ? 5 : 0) : (c.remap >= 3 ? c.remap : 0);
-    if (mode >= 3 && grid % (8 * (mode == 3 ? 8 : mode == 4 ? 2 : mode == 6 ? 64 : mode == 7 ? 128 : 32)) != 0) mode = 0;
-#define L(WW, DW, DY)                                                                                     \
-    hipLaunchKernelGGL((k_csr_slb<WW, ADD, DW, DY>), dim3(grid), dim3(256), 0, st, p.n, p.sbcode, p.dict, p.sval, x, y, \
-                       w, pwy, pyy, flag, gen, mode | g_launch_flags, p.run_sched, p.run_iters)
-#define LV(WW)                                \
-    if (p.sw == WW) {                         \
-        if (w && pyy) L(WW, true, true);      \
-        else if (w) L(WW, true, false);       \
-        else if (pyy) L(WW, false, true);     \
-        else L(WW, false, false);             \
-        return;                               \
-    }
-    SGM_SLB_WIDTHS(LV)
-#undef LV
-#undef L
-}
-
-// slots in flight per lane, nontemporal matrix loads, grid cap
-struct EllCfg { int u = 8, nt = 1, grid = 2048; };
-static EllCfg &ell_cfg()
-{
-    static EllCfg c;
-    static bool init = false;
-    if (!init) {
-        init = true;
-        if (c.grid > kMaxGrid) c.grid = kMaxGrid;
-    }
-    return c;
-}
+// k_ell_spmv: slots in flight per lane, grid cap
+constexpr int kEllU = 8, kEllGrid = 2048;
+static_assert(kEllGrid <= kMaxGrid, "one partial slot per workgroup");
 int ell_grid(const Part &p)
 {
     if (use_ell_colblock(p)) return ell_colblock_grid(p);
@@ -1225,86 +937,65 @@ int ell_grid(const Part &p)
         return (int)std::max<int64_t>(1, std::min<int64_t>(nsl, nsl >= 32768 ? kMaxGrid : kMaxGrid / 2));
     }
     int64_t g = ((int64_t)p.n + kBlock - 1) / kBlock;
-    int64_t cap = ell_cfg().grid;
+    int64_t cap = kEllGrid;
     // k_ell_do<16> holds 16 values + 16 x entries per lane: 77-88 VGPRs, 5 waves/SIMD with the fused
     // dots -- a grid-stride launch sized for 8 resident workgroups per CU would run a second round
     if (p.ecode && p.opt.ell_offset_dict && p.emdp == 16) cap = std::min<int64_t>(cap, (int64_t)5 * g_rt.num_cu);
     return (int)std::max<int64_t>(1, std::min<int64_t>(g, cap));
 }
 
-template <bool ADD>
-static void launch_ell(const Part &p, int grid, const double *x, double *y, const double *w,
-                       double *pwy, double *pyy, const int *flag, int gen)
+static void launch_ell(const Part &p, int grid, const SpmvArgs &a)
 {
     if (use_ell_colblock(p)) {         // random columns: products through LDS-resident x blocks, then ordered row sums
-        (void)launch_ell_colblock(p, grid, x, y, ADD, (g_launch_flags & 256) != 0, w, pwy, pyy, flag, gen);
+        (void)launch_ell_colblock(p, grid, a);
         return;
     }
     if (use_sliced_ell(p)) {           // structured ELLPACK in the sliced form: the CSR kernel as it is
         Part v;
         v.n = p.n; v.scode = p.scode; v.dict = p.dict; v.sval = p.sval; v.sw = p.sw;
         if (const SliceSched *ss = slice_sched(p, 0, p.n, grid)) { v.run_sched = ss->tab; v.run_iters = ss->iters; }
-        launch_csr_sl<ADD>(v, grid, x, y, w, pwy, pyy, flag, gen);
+        launch_csr_sl(v, grid, a);
         return;
     }
-    hipStream_t st = g_rt.stream;
-    const EllCfg &c = ell_cfg();
-    if (p.ecode && p.opt.ell_offset_dict) {
-#define LD(M, DW, DY)                                                                                   \
-    hipLaunchKernelGGL((k_ell_do<M, ADD, DW, DY>), dim3(grid), dim3(kBlock), 0, st, p.n, p.max_d, p.ecode, \
-                       p.dict, p.eval, x, y, w, pwy, pyy, flag, gen, g_launch_flags & 256)
-#define LDV(M)                                   \
-    {                                            \
-        if (w && pyy) LD(M, true, true);         \
-        else if (w) LD(M, true, false);          \
-        else if (pyy) LD(M, false, true);        \
-        else LD(M, false, false);                \
-    }
-        if (p.emdp == 4) LDV(4) else if (p.emdp == 8) LDV(8) else LDV(16)
-#undef LDV
+    with_flags(a, [&](auto flags) {
+        using F = decltype(flags);
+        if (p.ecode && p.opt.ell_offset_dict) {
+#define LD(M)                                                                                                               \
+    hipLaunchKernelGGL((k_ell_do<M, F::add, F::dot_w, F::dot_yy>), dim3(grid), dim3(kBlock), 0, g_rt.stream, p.n, p.max_d, p.ecode, p.dict, \
+                       p.eval, a.x, a.y, a.w, a.pwy, a.pyy, a.flag, a.gen, chain_bit(a))
+            if (p.emdp == 4) LD(4);
+            else if (p.emdp == 8) LD(8);
+            else LD(16);
 #undef LD
-        return;
-    }
-#define L(UU, NTT, DW, DY)                                                                          \
-    hipLaunchKernelGGL((k_ell_spmv<UU, NTT, ADD, DW, DY>), dim3(grid), dim3(kBlock), 0, st, p.n,     \
-                       p.max_d, p.ecol, p.eval, x, y, w, pwy, pyy, flag, gen, g_launch_flags & 256)
-#define LV(UU, NTT)                              \
-    {                                            \
-        if (w && pyy) L(UU, NTT, true, true);    \
-        else if (w) L(UU, NTT, true, false);     \
-        else if (pyy) L(UU, NTT, false, true);   \
-        else L(UU, NTT, false, false);           \
-    }
-    if (c.u >= 16) { if (c.nt) LV(16, true) else LV(16, false) }
-    else if (c.u <= 4) { if (c.nt) LV(4, true) else LV(4, false) }
-    else { if (c.nt) LV(8, true) else LV(8, false) }
-#undef LV
-#undef L
+            return;
+        }
+        hipLaunchKernelGGL((k_ell_spmv<kEllU, true, F::add, F::dot_w, F::dot_yy>), dim3(grid), dim3(kBlock), 0, g_rt.stream, p.n, p.max_d, p.ecol,
+                           p.eval, a.x, a.y, a.w, a.pwy, a.pyy, a.flag, a.gen, chain_bit(a));
+    });
 }
 
 // Workgroups of one kernel variant that fit on a CU at once (occupancy API, cached).
-// `v` is the TILE for the offset-dict kernel and VPT for the int32 kernel.
+// row_owner: k_csr_do with that TILE and column width; otherwise the streaming kernel.
 // The fused-dot variants of one (BLOCK, TILE, CW) family have the same occupancy as the plain kernel
 // (checked at build time with -Rpass-analysis=kernel-resource-usage: 8 waves/SIMD for tiles <= 1536,
 // 7 for the 1-byte-code kernel with larger tiles), so one grid serves every epilogue.
-int resident_per_cu(bool dict, int block, int v, int cw)
+int resident_per_cu(bool row_owner, int tile, int cw)
 {
     static std::vector<std::pair<int, int>> cache;
-    const int key = (dict ? 1 << 30 : 0) | (cw == 1 ? 1 << 29 : 0) | (block << 16) | v;
+    const int key = (row_owner ? 1 << 30 : 0) | (cw == 1 ? 1 << 29 : 0) | tile;
     for (auto &kv : cache)
         if (kv.first == key) return kv.second;
-    const void *fn = nullptr;
-#define PICK_DO(B, T)                                                                                   \
-    if (dict && block == B && v == T)                                                                   \
-        fn = cw == 1 ? (const void *)k_csr_do<B, T, 1, false, true, false> : (const void *)k_csr_do<B, T, 4, false, true, false>;
-#define PICK_ST(B, V) if (!dict && block == B && v == V) fn = (const void *)k_csr_spmv<B, V, true, false, false, false>;
-    SGM_DO_VARIANTS(PICK_DO)
-    PICK_ST(256, 2) PICK_ST(256, 4) PICK_ST(256, 8) PICK_ST(512, 2) PICK_ST(512, 4) PICK_ST(512, 8) PICK_ST(1024, 2) PICK_ST(1024, 4)
+    const void *fn = row_owner ? nullptr : (const void *)k_csr_spmv<kSpmvBlock, kSpmvVpt, true, false, false, false>;
+#define PICK_DO(T)                                                                                      \
+    if (row_owner && tile == T) {                                                                       \
+        if (cw != 1) fn = (const void *)k_csr_do<kSpmvBlock, T, 4, false, true, false>;                 \
+        else if constexpr (T <= kDoMaxCodeTile) fn = (const void *)k_csr_do<kSpmvBlock, T, 1, false, true, false>; \
+    }
+    SGM_DO_TILES(PICK_DO)
 #undef PICK_DO
-#undef PICK_ST
     int nb = 0;
-    if (!fn || hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, block, 0) != hipSuccess || nb < 1)
-        nb = 2048 / block;
+    if (!fn || hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, kSpmvBlock, 0) != hipSuccess || nb < 1)
+        nb = 2048 / kSpmvBlock;
     cache.emplace_back(key, nb);
     return nb;
 }
@@ -1349,8 +1040,7 @@ void free_slice_sched(Part &p)
     p.nsched = 0;
 }
 
-static void launch_range(sgm_mat A, const Part &p, const RowRange &r, const double *x, double *y, bool add,
-                         const double *w, double *pwy, double *pyy, const int *flag_done, int gen)
+static void launch_range(const Part &p, const RowRange &r, const SpmvArgs &a)
 {
     // a row range is the same kernel on shifted pointers: rowptr entries stay absolute offsets
     // into val/col/code; the offset-dict kernel forms columns as row + offset, so x shifts too
@@ -1375,32 +1065,20 @@ static void launch_range(sgm_mat A, const Part &p, const RowRange &r, const doub
         v.sl_win0 = p.sl_win0 ? p.sl_win0 + r.lo / (kSlRows * p.sl_gs) : nullptr; v.sl_span = p.sl_span;
     }
     const bool dict = use_offset_dict(p);
-    const double *xs = dict ? x + r.lo : x;
-    double *ys = y + r.lo;
-    const double *ws = w ? w + r.lo : nullptr;
-    double *pw = pwy ? pwy + r.part_off : nullptr, *py = pyy ? pyy + r.part_off : nullptr;
-    if (sliced) {
-        if (add) launch_csr_sl<true>(v, r.grid, xs, ys, ws, pw, py, flag_done, gen);
-        else launch_csr_sl<false>(v, r.grid, xs, ys, ws, pw, py, flag_done, gen);
-    } else if (slicedb) {
-        if (add) launch_csr_slb<true>(v, r.grid, xs, ys, ws, pw, py, flag_done, gen);
-        else launch_csr_slb<false>(v, r.grid, xs, ys, ws, pw, py, flag_done, gen);
-    } else if (sliced32) {            // absolute columns: x is not shifted
-        if (add) launch_csr_sl32<true>(v, r.grid, x, ys, ws, pw, py, flag_done, gen);
-        else launch_csr_sl32<false>(v, r.grid, x, ys, ws, pw, py, flag_done, gen);
-    } else if (sell) {
-        if (add) launch_csr_sell<true>(v, r.grid, x, ys, ws, pw, py, flag_done, gen);
-        else launch_csr_sell<false>(v, r.grid, x, ys, ws, pw, py, flag_done, gen);
-    } else if (use_row_owner(p)) {
-        if (add) launch_csr_do<true>(v, r.grid, xs, ys, ws, pw, py, flag_done, gen);
-        else launch_csr_do<false>(v, r.grid, xs, ys, ws, pw, py, flag_done, gen);
-    } else if (use_row_lines(p)) {
-        if (add) launch_csr_rl<true>(v, r.grid, xs, ys, ws, pw, py, flag_done, gen);
-        else launch_csr_rl<false>(v, r.grid, xs, ys, ws, pw, py, flag_done, gen);
-    } else {
-        if (add) launch_csr<true>(v, r.grid, xs, ys, ws, pw, py, flag_done, gen);
-        else launch_csr<false>(v, r.grid, xs, ys, ws, pw, py, flag_done, gen);
-    }
+    // the range's launch: y, w and the partials shift with the rows; x shifts for the kernels that form columns as row + offset
+    SpmvArgs ar = a;
+    ar.y = a.y + r.lo;
+    ar.w = a.w ? a.w + r.lo : nullptr;
+    ar.pwy = a.pwy ? a.pwy + r.part_off : nullptr;
+    ar.pyy = a.pyy ? a.pyy + r.part_off : nullptr;
+    if (dict && !sliced32 && !sell) ar.x = a.x + r.lo;
+    if (sliced) launch_csr_sl(v, r.grid, ar);
+    else if (slicedb) launch_csr_slb(v, r.grid, ar);
+    else if (sliced32) launch_csr_sl32(v, r.grid, ar);            // absolute columns: x is not shifted
+    else if (sell) launch_csr_sell(v, r.grid, ar);
+    else if (use_row_owner(p)) launch_csr_do(v, r.grid, ar);
+    else if (use_row_lines(p)) launch_csr_rl(v, r.grid, ar);
+    else launch_csr(v, r.grid, ar);
 }
 
 static int composite_spmv(sgm_mat A, const double *x, double *y, bool add, const SpmvDots *dots,
@@ -1417,7 +1095,6 @@ int spmv_parts(sgm_mat A, const double *const *x, double *const *y, bool add,
     if (A->fmt == SGM_FMT_CSR)
         for (const Part &p : A->parts)
             if (p.lean && !(lean_sell(p) ? use_sell(p) : use_sliced(p))) SGM_TRY(csr_need_arrays(p));
-    g_launch_flags = chain ? 256 : 0;
     bool exchange = false;
     if (A->distributed() && !halo_ready)
         for (const Part &p : A->parts) exchange = exchange || !p.nbrs.empty();
@@ -1451,22 +1128,21 @@ int spmv_parts(sgm_mat A, const double *const *x, double *const *y, bool add,
         }
         for (size_t ip = 0; ip < P; ++ip) {
             const Part &p = A->parts[ip];
-            const double *w = dots && dots->w ? dots->w[ip] : nullptr;
-            double *pwy = dots && dots->part_wy ? dots->part_wy[ip] : nullptr;
-            double *pyy = dots && dots->part_yy ? dots->part_yy[ip] : nullptr;
+            const SpmvArgs a = {x[ip], y[ip], add, chain, dots && dots->w ? dots->w[ip] : nullptr,
+                                dots && dots->part_wy ? dots->part_wy[ip] : nullptr,
+                                dots && dots->part_yy ? dots->part_yy[ip] : nullptr, flag_done, gen};
             if (A->fmt != SGM_FMT_CSR) {
                 if (pass == 1) continue;
                 const int grid = ell_grid(p);
                 if (grid_out) *grid_out = grid;
-                if (add) launch_ell<true>(p, grid, x[ip], y[ip], w, pwy, pyy, flag_done, gen);
-                else launch_ell<false>(p, grid, x[ip], y[ip], w, pwy, pyy, flag_done, gen);
+                launch_ell(p, grid, a);
                 continue;
             }
             if (use_ell_colblock(p)) {         // a CSR matrix with scattered columns (no halo: single-GPU parts only)
                 if (pass == 1) continue;
                 const int grid = ell_colblock_grid(p);
                 if (grid_out) *grid_out = grid;
-                SGM_TRY(launch_ell_colblock(p, grid, x[ip], y[ip], add, chain, w, pwy, pyy, flag_done, gen));
+                SGM_TRY(launch_ell_colblock(p, grid, a));
                 continue;
             }
             RowRange r[3];
@@ -1478,12 +1154,11 @@ int spmv_parts(sgm_mat A, const double *const *x, double *const *y, bool add,
             for (int k = 0; k < nr; ++k) {
                 const bool needs_halo = !(split && k == 0) && p.n_halo > 0;
                 if ((pass == 1) != needs_halo) continue;
-                launch_range(A, p, r[k], x[ip], y[ip], add, w, pwy, pyy, flag_done, gen);
+                launch_range(p, r[k], a);
             }
         }
     }
     if (prof_on()) prof_end(exchange ? PH_BOUNDARY : PH_INTERIOR, g_rt.stream);
-    g_launch_flags = 0;
     SGM_HIP(hipGetLastError());
     return SGM_OK;
 }
@@ -1494,7 +1169,7 @@ __global__ __launch_bounds__(kBlock) void k_dot_wy_yy(int64_t n, const double *_
                                                       double *part_yy, const int *flag_done, int gen)
 {
     __shared__ double red[kBlock / 64];
-    if (flag_done) { const int st = *flag_done; if (st && gen >= st) return; }
+    if (stopped(flag_done, gen)) return;
     double a = 0.0, b = 0.0;
     const int64_t stride = (int64_t)gridDim.x * kBlock;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
@@ -1553,7 +1228,8 @@ void set_interior_range(Part &p, const int32_t *ptr1, const int32_t *node1)
     if (p.n_halo == 0 || p.n == 0) return;
     // ranges are cut at row-block boundaries of the kernel that will run them (512-row slices for the
     // sliced kernel; a multiple of the other kernels' 256-row blocks, so they can run the ranges too)
-    const int B = p.sl_val ? kSellSigma : (p.scode || p.scol || p.sbcode) ? std::max(kSlRows, spmv_cfg().block) : spmv_cfg().block;      // (SELL: whole sort windows)
+    static_assert(kSlRows % kSpmvBlock == 0, "a slice is whole row blocks");
+    const int B = p.sl_val ? kSellSigma : (p.scode || p.scol || p.sbcode) ? kSlRows : kSpmvBlock;      // (SELL: whole sort windows)
     const int32_t nb = (p.n + B - 1) / B;
     int32_t best_lo = 0, best_len = 0, run_lo = 0, run_len = 0;
     for (int32_t b = 0; b < nb; ++b) {

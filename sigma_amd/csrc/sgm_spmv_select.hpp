@@ -41,24 +41,50 @@ static bool lean_applies(const Part &p) { return p.opt.csr_lean && (lean_sliced(
 // launch helpers
 // ---------------------------------------------------------------------------------
 
-// Launch configuration of the CSR kernel (block, vpt, nt, maxgrid, remap: fixed; the sweeps that chose them are in CHANGELOG.md)
-struct SpmvCfg { int block = 256, vpt = 2, nt = 1, maxgrid = 0, remap = 1, do_vpt = 0; };   // 0 = automatic
-static SpmvCfg &spmv_cfg()
+// Launch configuration of the CSR kernels: 256-thread workgroups own 256 consecutive rows; the streaming kernel stages
+// 2 * 256 * kSpmvVpt products per pass (fixed; the sweeps that chose them are in CHANGELOG.md)
+constexpr int kSpmvBlock = 256, kSpmvVpt = 2;
+
+// The `remap` argument of the CSR kernels: the slice-map mode of a sliced launch (slice_map_mode) in the low byte, and
+// kChainBit: chained accumulation -- the row sum continues from y(i) (transpose products).
+constexpr int kSliceMapBits = 255, kChainBit = 256;
+constexpr int kSliceMapGroup = 32;      // G of the XCD-block-cyclic slice map (first_slice, sgm_spmv_device.hpp)
+// 1 = XCD-block-cyclic slices below 32768 slices, 0 = plain round-robin on the 8192 grids above that (measured: 300^3 363 vs
+// 358 us) and wherever the grid is not a multiple of 8 G (the cyclic map is a permutation only there)
+static int slice_map_mode(int grid, int64_t n)
 {
-    static SpmvCfg c;
-    static bool init = false;
-    if (!init) {
-        init = true;
-        if (c.maxgrid > kMaxGrid) c.maxgrid = kMaxGrid;
-        // only instantiated (block, vpt) pairs: anything else would launch a kernel of another shape
-        if (c.block != 256 && c.block != 512 && c.block != 1024) c.block = 256;
-        if (c.vpt != 2 && c.vpt != 4 && c.vpt != 8) c.vpt = 2;
-        if (c.block == 1024 && c.vpt == 8) c.vpt = 4;
-    }
-    return c;
+    return grid % (8 * kSliceMapGroup) == 0 && (grid <= kMaxGrid / 2 || n < (int64_t)32768 * kSlRows) ? 1 : 0;
 }
 
-int resident_per_cu(bool dict, int block, int v, int cw = 4);         // (sgm_spmv.hip)
+// What one product launch carries besides the matrix part and its grid: y = A x (add: y = y + A x; chain: kChainBit), the
+// operands of the fused dots (w.y when w, y.y when pyy; one partial per workgroup), the stop flag and the generation.
+struct SpmvArgs {
+    const double *x; double *y; bool add, chain;
+    const double *w; double *pwy, *pyy;
+    const int *flag; int gen;
+};
+// The run-time add / fused-dot choice of a launch as compile-time flags: f is called once with a SpmvFlags<...> value, whose
+// type carries the three template arguments of the product kernels.  Every product launcher goes through here.
+template <bool ADD, bool DOT_W, bool DOT_YY>
+struct SpmvFlags { static constexpr bool add = ADD, dot_w = DOT_W, dot_yy = DOT_YY; };
+template <class F>
+static void with_flags(const SpmvArgs &a, F &&f)
+{
+    const bool dot_w = a.w != nullptr, dot_yy = a.pyy != nullptr;
+    if (a.add) {
+        if (dot_w && dot_yy) f(SpmvFlags<true, true, true>{});
+        else if (dot_w) f(SpmvFlags<true, true, false>{});
+        else if (dot_yy) f(SpmvFlags<true, false, true>{});
+        else f(SpmvFlags<true, false, false>{});
+    } else {
+        if (dot_w && dot_yy) f(SpmvFlags<false, true, true>{});
+        else if (dot_w) f(SpmvFlags<false, true, false>{});
+        else if (dot_yy) f(SpmvFlags<false, false, true>{});
+        else f(SpmvFlags<false, false, false>{});
+    }
+}
+
+int resident_per_cu(bool row_owner, int tile, int cw);                 // (sgm_spmv.hip)
 static const SliceSched *slice_sched(const Part &p, int32_t lo, int32_t hi, int grid);
 void free_slice_sched(Part &p);                                         // (sgm_spmv.hip)
 int ell_grid(const Part &p);
@@ -68,14 +94,10 @@ int ell_colblock_grid(const Part &p);
 int build_ell_colblock(Part &p);
 int refresh_ell_colblock_values(Part &p);
 void free_ell_colblock(Part &p);
-int launch_ell_colblock(const Part &p, int grid, const double *x, double *y, bool add, bool chain, const double *w,
-                        double *pwy, double *pyy, const int *flag, int gen);
+int launch_ell_colblock(const Part &p, int grid, const SpmvArgs &a);
 int64_t ell_colblock_resident_bytes(const Part &p);
 int64_t ell_colblock_matvec_bytes(const Part &p);
-// k_csr_do exists for 256- and 512-thread workgroups only; with any other block size the
-// matrices it would serve take the streaming kernel (which has the 1024-thread variants) instead
-static bool do_block_ok() { const int b = spmv_cfg().block; return b == 256 || b == 512; }
-static bool use_offset_dict(const Part &p) { return (p.code || (p.lean && p.dict)) && p.opt.csr_offset_dict && do_block_ok(); }
+static bool use_offset_dict(const Part &p) { return (p.code || (p.lean && p.dict)) && p.opt.csr_offset_dict; }
 static bool use_sliced(const Part &p) { return p.scode && p.opt.csr_sliced && p.opt.csr_offset_dict; }
 static bool use_sliced32(const Part &p) { return p.scol && p.opt.csr_sliced && !p.ecol; }
 static bool use_slicedb(const Part &p) { return p.sbcode && p.opt.csr_sliced && p.opt.csr_offset_dict; }
@@ -87,7 +109,7 @@ static bool use_row_owner(const Part &p)
 {
     // (rows of 33..64 entries, banded: 809-822 us against 906 with k_csr_rl and 1100-1150 with k_csr_spmv; beyond 64 the
     // few lanes that own a tile's rows walk too long: 64..128 entries 1160 us against 890 with k_csr_rl)
-    return use_offset_dict(p) || (do_block_ok() && p.opt.csr_row_owner && p.max_row > 0 && p.max_row <= 64);
+    return use_offset_dict(p) || (p.opt.csr_row_owner && p.max_row > 0 && p.max_row <= 64);
 }
 
 // long rows without a dictionary: the line-staged row-owner kernel (k_csr_rl).  A block takes as many passes as its
@@ -105,21 +127,19 @@ static bool use_row_lines(const Part &p)
 }
 int row_lines_resident_per_cu();          // (sgm_spmv.hip: asks the runtime about k_csr_rl)
 
-// (BLOCK, TILE) instantiations of the offset-dict kernel.  TILE = entries staged in LDS per
+// TILE instantiations of the offset-dict kernel.  TILE = entries staged in LDS per
 // pass (9 bytes each); the launcher picks the smallest one that holds a whole row block of
 // average density (+ alignment slack), so that a row block is one load phase + one gather
 // phase and the LDS footprint stays small enough for 8 workgroups per CU.
-#define SGM_DO_VARIANTS(X) X(256, 1024) X(256, 1536) X(256, 1920) X(256, 2048) X(256, 4096) X(512, 2048) X(512, 3072) X(512, 3840)
+#define SGM_DO_TILES(X) X(1024) X(1536) X(1920) X(2048) X(4096)
+constexpr int kDoMaxCodeTile = 2048;       // the largest tile of the 1-byte-code form (do_tile_for)
 static int do_tile_for(const Part &p)
 {
-    const SpmvCfg &c = spmv_cfg();
-    static const int t256[] = {1024, 1536, 1920, 2048, 4096}, t512[] = {2048, 3072, 3840};
-    const int *tiles = c.block == 512 ? t512 : t256;
+    static const int tiles[] = {1024, 1536, 1920, 2048, 4096};
     // (the 4096-entry tile serves int32 columns only -- long rows: 33..64 entries 794 -> 770 us, 20..40 746 -> 719;
     // the 1-byte-code form keeps its 2048, measured with seven workgroups per CU)
-    const int nt = c.block == 512 ? 3 : (use_offset_dict(p) ? 4 : 5);
-    if (c.do_vpt) return tiles[std::min(std::max(c.do_vpt - 1, 0), nt - 1)];     // tuning override: 1..nt
-    const double per_block = (double)p.nnz / (p.n > 0 ? p.n : 1) * c.block + 4;
+    const int nt = use_offset_dict(p) ? 4 : 5;
+    const double per_block = (double)p.nnz / (p.n > 0 ? p.n : 1) * kSpmvBlock + 4;
     for (int i = 0; i < nt; ++i)
         if (per_block <= tiles[i]) return tiles[i];
     return tiles[nt - 1];
@@ -130,19 +150,17 @@ static int do_tile_for(const Part &p)
 // a tail, a smaller one leaves CUs idle (measured: 7-point, 19.5 KiB LDS: 1536 beats 2048).
 static int grid_for_rows(const Part &p, int64_t rows, int64_t limit, bool dots = true)
 {
-    const SpmvCfg &c = spmv_cfg();
-    const int blk = any_sliced(p) ? kSlRows : use_row_lines(p) ? 256 : c.block;
+    const int blk = any_sliced(p) ? kSlRows : kSpmvBlock;
     const int64_t nrb = (rows + blk - 1) / blk;
     int64_t g = ((nrb + 7) / 8) * 8;
-    int64_t cap = c.maxgrid;
+    int64_t cap;
     // round-robin slices, not a persistent resident grid: 4096 workgroups; 8192 from 32768 slices on
     // (n >= 1.7e7: 464^3 1.54 -> 1.45 ms, 300^3 355 -> 345 us; below that the consumers' re-reduction of more partials costs more)
     // a product WITHOUT fused dots takes the 8192 grid at every size (C2: 98.5 -> 95.9 us with the block-cyclic map); with
     // them the 4096 one below 32768 slices (8192 partials per dot cost the CG update kernels more than the product gains)
-    if (cap <= 0 && any_sliced(p)) cap = (nrb >= 32768 || !dots) ? kMaxGrid : kMaxGrid / 2;
-    if (cap <= 0 && use_row_lines(p)) cap = (int64_t)row_lines_resident_per_cu() * g_rt.num_cu;
-    if (cap <= 0) cap = (int64_t)resident_per_cu(use_row_owner(p), c.block, use_row_owner(p) ? do_tile_for(p) : c.vpt,
-                                                 use_offset_dict(p) ? 1 : 4) * g_rt.num_cu;
+    if (any_sliced(p)) cap = (nrb >= 32768 || !dots) ? kMaxGrid : kMaxGrid / 2;
+    else if (use_row_lines(p)) cap = (int64_t)row_lines_resident_per_cu() * g_rt.num_cu;
+    else cap = (int64_t)resident_per_cu(use_row_owner(p), use_row_owner(p) ? do_tile_for(p) : 0, use_offset_dict(p) ? 1 : 4) * g_rt.num_cu;
     if (cap > limit) cap = limit;
     if (g > cap) g = cap / 8 * 8;
     if (g < 8) g = 8;
