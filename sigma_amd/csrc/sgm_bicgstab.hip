@@ -280,39 +280,23 @@ static int run_bicgstab_small(sgm_solver s, sgm_mat A, double *x, const double *
     const Part &p = A->parts[0];
     PartWork &w = s->work[0];
     const bool jac = pc && pc_kind(pc) == SGM_PC_JACOBI;
-    const bool sliced = cg_small_sliced(p);
     const size_t npad = (size_t)((p.n + 1) & ~1);
     const size_t lds = ((s->seq ? 3 : 1) * npad + 32) * sizeof(double);
-    const int64_t chunk = s->small_chunk();
-    int flag = 0; int64_t iters = 0; double res = 0.0;
-    *ran = true;
-    for (int resume = 0;; resume = 1) {
-        int64_t it_end = iters + chunk;
-        if (s->max_iter > 0) it_end = std::min<int64_t>(it_end, s->max_iter);
-#define LS(J, S, Q)                                                                                                  \
-    do {                                                                                                             \
-        if (!allow_lds((const void *)k_bicgstab_small<4, J, S, Q>, lds)) { *ran = false; return SGM_OK; }             \
-        hipLaunchKernelGGL((k_bicgstab_small<4, J, S, Q>), dim3(1), dim3(1024), lds, g_rt.stream, p.n, p.sw,          \
-                           S ? reinterpret_cast<const int32_t *>(p.scode) : (const int32_t *)p.rowptr,                \
-                           S ? (const int32_t *)p.dict : (const int32_t *)p.col, S ? (const double *)p.sval : (const double *)p.val, \
-                           x, b, jac ? pc_idiag(pc, 0) : nullptr, s->tolerance, it_end, resume, w.vec[W_R], w.vec[W_R0], \
-                           w.vec[W_P], w.vec[W_V], w.slots, w.flag, w.iters, w.res, w.history, s->hist_cap);          \
-    } while (0)
-#define LSQ(J, S) do { if (s->seq) LS(J, S, true); else LS(J, S, false); } while (0)
-        if (sliced) { if (jac) LSQ(true, true); else LSQ(false, true); }
-        else { if (jac) LSQ(true, false); else LSQ(false, false); }
-#undef LSQ
-#undef LS
-        SGM_HIP(hipGetLastError());
-        SGM_TRY(read_state(s, &flag, &iters, &res));
-        if (flag || (s->max_iter > 0 && iters >= s->max_iter)) break;
-    }
-    s->last_iterations = iters;
-    s->res2 = res;
-    s->converged = flag;
-    return SGM_OK;
+    auto launch = [&](int64_t it_end, int resume, const CoopArgs &) {
+        return with_flag(jac, [&](auto J) { return with_flag(cg_small_sliced(p), [&](auto SL) { return with_flag(s->seq, [&](auto Q) {
+            constexpr bool S = decltype(SL)::value;
+            auto *k = k_bicgstab_small<4, decltype(J)::value, S, decltype(Q)::value>;
+            if (!allow_lds((const void *)k, lds)) return false;
+            hipLaunchKernelGGL(k, dim3(1), dim3(1024), lds, g_rt.stream, p.n, p.sw,
+                               S ? reinterpret_cast<const int32_t *>(p.scode) : (const int32_t *)p.rowptr,
+                               S ? (const int32_t *)p.dict : (const int32_t *)p.col, S ? (const double *)p.sval : (const double *)p.val,
+                               x, b, jac ? pc_idiag(pc, 0) : nullptr, s->tolerance, it_end, resume, w.vec[W_R], w.vec[W_R0],
+                               w.vec[W_P], w.vec[W_V], w.slots, w.flag, w.iters, w.res, w.history, s->hist_cap);
+            return true;
+        }); }); });
+    };
+    return run_chunked(s, A, x, nullptr, launch, ran);
 }
-
 
 // ---- BiCGStab on a mid-sized system: the whole solve in ONE cooperative launch ------------------------------------------
 // k_bicgstab_small's statements (bicgstab_solvers.f90:124-177 / :182-237 with a diagonal M) spread over G workgroups the way
@@ -349,23 +333,25 @@ __global__ __launch_bounds__(1024) void k_bicg_coop(
     double *rh = red + 48;                               // r on the halo rows (2 H)
     double *xs = rh + 2 * H, *r0s = xs + RPW;
     __shared__ int32_t dl[16];
-    if (XL && (blockIdx.x & 7) != 0) return;
-    const int tid = threadIdx.x, G = XL ? (int)(gridDim.x >> 3) : (int)gridDim.x, wg = XL ? (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+    if (coop_idle<XL>()) return;
+    const CoopGeom g = coop_geom<RPW, XL>(n);
+    const int tid = threadIdx.x, G = g.G, wg = g.wg;
     const int reps = XL ? 1 : kCoopReplicas;
-    const int32_t r0w = wg * RPW, r1w = min(n, r0w + RPW);
+    const int32_t r0w = g.r0, r1w = g.r1;
     double *gz_r = gz, *gz_w = gz + n, *gz_v = gz + 2 * (size_t)n;
     if (tid < 16) dl[tid] = dict[tid];
     int h = h0;
     auto handoff1 = [&](double mine, double &total) {
-        const bool ok_ = coop_handoff(slots, h, mine, wg, G, XL, abort, spin_limit, red, lds_ok, &total, reps, nullptr, true);
+        const bool ok_ = coop_handoff<1>(slots, h, mine, 0.0, wg, G, XL, abort, spin_limit, red, lds_ok, &total, nullptr, reps, true);
         ++h;
         return ok_;
     };
     auto handoff2 = [&](double ma, double mb, double &ta, double &tb) {
-        const bool ok_ = coop_handoff2(slots, h, ma, mb, wg, G, XL, abort, spin_limit, red, lds_ok, &ta, &tb, reps);
+        const bool ok_ = coop_handoff<2>(slots, h, ma, mb, wg, G, XL, abort, spin_limit, red, lds_ok, &ta, &tb, reps, true);
         ++h;
         return ok_;
     };
+    // the resident matrix and the row sums: the same text as k_cg_coop's, written out in both on purpose (sgm_coop.hpp, header comment)
     uint32_t cwr[RMAX];
     double mv[RMAX][SW > 0 ? SW : 1];
 #pragma unroll
@@ -412,25 +398,9 @@ __global__ __launch_bounds__(1024) void k_bicg_coop(
         for (int u = 0; u < RMAX; ++u) q[u] = 0.0 + q[u];
     };
     // the boundary rows of an own-row vector to an exchange vector
-    auto publish = [&](double *dst, const double (&w)[RMAX]) {
-#pragma unroll
-        for (int u = 0; u < RMAX; ++u) {
-            const int32_t li = tid + u * BLOCK, i = r0w + li;
-            if (i < r1w && (li < H || i >= r1w - H)) st_pub(dst + i, w[u], XL);
-        }
-    };
-    auto block_dot = [&](const double (&prod)[RMAX]) {
-        double sacc = 0.0;
-#pragma unroll
-        for (int u = 0; u < RMAX; ++u) sacc += prod[u];
-        return block_sum<BLOCK>(sacc, red);
-    };
-    auto block_dot2 = [&](const double (&pa)[RMAX], const double (&pb)[RMAX], double &sa, double &sb) {
-        double a = 0.0, c = 0.0;
-#pragma unroll
-        for (int u = 0; u < RMAX; ++u) { a += pa[u]; c += pb[u]; }
-        block_sum2<BLOCK>(a, c, red, sa, sb);
-    };
+    auto publish = [&](double *dst, const double (&w)[RMAX]) { coop_publish<RMAX>(dst, w, g, H, XL); };
+    auto block_dot = [&](const double (&prod)[RMAX]) { return coop_dot<RMAX>(prod, red); };
+    auto block_dot2 = [&](const double (&pa)[RMAX], const double (&pb)[RMAX], double &sa, double &sb) { coop_dot2<RMAX>(pa, pb, red, sa, sb); };
     double xr[LDSV ? 1 : RMAX], rr[RMAX], r0[LDSV ? 1 : RMAX], pp[RMAX], vv[RMAX], prod0[RMAX], prod1[RMAX];
     auto X = [&](int u) -> double & { return LDSV ? xs[tid + u * BLOCK] : xr[LDSV ? 0 : u]; };
     auto R0 = [&](int u) -> double & { return LDSV ? r0s[tid + u * BLOCK] : r0[LDSV ? 0 : u]; };
@@ -451,7 +421,7 @@ __global__ __launch_bounds__(1024) void k_bicg_coop(
     if (XL) {                                              // the proof of co-location (k_cg_coop)
         double total;
         const double mark = __longlong_as_double((long long)(1023 + 6 * xcc_id()) << 52);
-        ok = coop_handoff(slots, h, mark, wg, G, false, abort, spin_limit, red, lds_ok, &total, 1, nullptr, true);
+        ok = coop_handoff<1>(slots, h, mark, 0.0, wg, G, false, abort, spin_limit, red, lds_ok, &total, nullptr, 1, true);
         ++h;
         if (ok && total != mark * (double)G) {
             if (tid == 0) __hip_atomic_store(abort, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -597,7 +567,7 @@ __global__ __launch_bounds__(1024) void k_bicg_coop(
     }
 }
 
-// hand-offs of one launch: 3 per iteration, + 1 at the start of a fresh solve, + 1 for the one-XCD variant's proof
+// (3 hand-offs per iteration; three exchange vectors: r, w, v)
 static int run_bicg_coop(sgm_solver s, sgm_mat A, double *x, const double *b, sgm_pc pc, int rmax, int H, bool xl, bool *ran)
 {
     const Part &p = A->parts[0];
@@ -606,100 +576,34 @@ static int run_bicg_coop(sgm_solver s, sgm_mat A, double *x, const double *b, sg
     const int64_t rpw = (int64_t)rmax * 1024;
     const int G = (int)((p.n + rpw - 1) / rpw);
     const size_t lds = (size_t)(rpw + 4 * H + 48 + (rmax >= 2 ? 2 * rpw : 0)) * sizeof(double);      // p / s + halo, scratch, r's halo, (x, r0)
-    const size_t nx = 3 * (size_t)p.n;                                                                // exchange vectors: r, w, v
-    *ran = false;
-    if (!s->coop_buf) {
-        if (dalloc(&s->coop_buf, nx + (size_t)kCoopSlotDoubles + 64) != SGM_OK) return SGM_OK;
-        SGM_TRY(coop_arm(s, nx));
-    }
-    double *gz = s->coop_buf, *slots = gz + nx;
-    int *abortw = reinterpret_cast<int *>(slots + (size_t)kCoopSlotDoubles);
-    int flag = 0; int64_t iters = 0; double res = 0.0;
-    if (!s->x_backup) SGM_TRY(dalloc(&s->x_backup, (size_t)p.n + 2));            // (as in run_cg_coop: the caller's x, for an aborted first launch)
-    SGM_HIP(hipMemcpyAsync(s->x_backup, x, (size_t)p.n * 8, hipMemcpyDeviceToDevice, g_rt.stream));
-    for (int resume = 0;; resume = 1) {
-        int64_t it_end = iters + s->small_chunk();
-        if (s->max_iter > 0) it_end = std::min<int64_t>(it_end, s->max_iter);
-        const int spin = s->opt.coop_spin_limit > 0 ? s->opt.coop_spin_limit : kCoopSpinLimit;
-#define LB(R, J, W, X)                                                                                                 \
-    do {                                                                                                             \
-        if (!allow_lds((const void *)k_bicg_coop<R, J, W, X>, lds)) return SGM_OK;                                    \
-        hipLaunchKernelGGL((k_bicg_coop<R, J, W, X>), dim3(X ? 8 * G : G), dim3(1024), lds, g_rt.stream, p.n, p.sw, H, (const uint32_t *)p.scode, \
-                           (const int32_t *)p.dict, (const double *)p.sval, x, b, jac ? pc_idiag(pc, 0) : nullptr, s->tolerance, it_end,  \
-                           resume, w.vec[W_R], w.vec[W_R0], w.vec[W_P], w.vec[W_V], w.slots, gz, slots, abortw, s->coop_base & 3, spin,  \
-                           w.flag, w.iters, w.res, w.history, s->hist_cap);                                           \
-    } while (0)
-#define LBJ(R, W, X) do { if (jac) LB(R, true, W, X); else LB(R, false, W, X); } while (0)
-#define LBX(R, W) do { if (xl) LBJ(R, W, true); else LBJ(R, W, false); } while (0)
+    auto launch = [&](int64_t it_end, int resume, const CoopArgs &c) {
+        auto go = [&](auto R, auto W) {                  // k_bicg_coop<R, jac, W, xl>
+            return with_flag(jac, [&](auto J) { return with_flag(xl, [&](auto X) {
+                auto *k = k_bicg_coop<decltype(R)::value, decltype(J)::value, decltype(W)::value, decltype(X)::value>;
+                if (!allow_lds((const void *)k, lds)) return false;
+                hipLaunchKernelGGL(k, dim3(decltype(X)::value ? 8 * G : G), dim3(1024), lds, g_rt.stream, p.n, p.sw, H, (const uint32_t *)p.scode,
+                                   (const int32_t *)p.dict, (const double *)p.sval, x, b, jac ? pc_idiag(pc, 0) : nullptr, s->tolerance, it_end,
+                                   resume, w.vec[W_R], w.vec[W_R0], w.vec[W_P], w.vec[W_V], w.slots, c.gz, c.slots, c.abort, c.h0, c.spin,
+                                   w.flag, w.iters, w.res, w.history, s->hist_cap);
+                return true;
+            }); });
+        };
         // the matrix in registers where it fits beside the five vectors (one row per thread: any slice width; two: <= 5 slots)
-        constexpr bool stream_env = false;
-        if (rmax == 1 && !stream_env) { if (p.sw == 3) LBX(1, 3); else if (p.sw == 5) LBX(1, 5); else if (p.sw == 7) LBX(1, 7); else LBX(1, 8); }
-        else if (rmax == 2 && !stream_env && p.sw <= 5) { if (p.sw == 3) LBX(2, 3); else LBX(2, 5); }
-        else if (rmax == 1) LBX(1, 0);
-        else if (rmax == 2) LBX(2, 0);
-        else LBX(4, 0);
-#undef LBX
-#undef LBJ
-#undef LB
-        SGM_HIP(hipGetLastError());
-        int habort = 0;
-        SGM_HIP(hipMemcpyAsync(&habort, abortw, sizeof(int), hipMemcpyDeviceToHost, g_rt.stream));
-        SGM_TRY(read_state(s, &flag, &iters, &res));
-        if (habort) {
-            SGM_TRY(coop_arm(s, nx));
-            if (!resume) SGM_HIP(hipMemcpyAsync(x, s->x_backup, (size_t)p.n * 8, hipMemcpyDeviceToDevice, g_rt.stream));
-            if (xl) s->coop_xl_retired = true;
-            else {
-                fprintf(stderr, "[sigma_hip] cooperative BiCGStab gave up waiting for a workgroup (grid not co-resident / shared GPU?): "
-                                "this solver takes the launch loop from now on\n");
-                s->coop_retired = true;
-            }
-            if (resume) return fail(SGM_ERR_HIP, "cooperative BiCGStab aborted in a continued launch");
-            return SGM_OK;
-        }
-        s->coop_base = (int)((s->coop_base + 3 * (iters - (resume ? s->coop_iters0 : 0)) + (resume ? 0 : 1) + (xl ? 1 : 0)) & 3);
-        s->coop_iters0 = iters;
-        if (flag || (s->max_iter > 0 && iters >= s->max_iter)) break;
-    }
-    *ran = true;
-    s->last_iterations = iters;
-    s->res2 = res;
-    s->converged = flag;
-    if (trace_on())
-        fprintf(stderr, "[sigma_hip] bicgstab: one cooperative launch per %lld iterations, %s, %d workgroups x %lld rows\n", (long long)s->small_chunk(),
-                xl ? "on one XCD" : "all CUs", G, (long long)rpw);
-    return SGM_OK;
+        if (rmax == 1) return with_slots(p.sw, [&](auto W) { return go(Int<1>{}, W); });
+        if (rmax == 2 && p.sw == 3) return go(Int<2>{}, Int<3>{});
+        if (rmax == 2 && p.sw <= 5) return go(Int<2>{}, Int<5>{});
+        if (rmax == 2) return go(Int<2>{}, Int<0>{});
+        return go(Int<4>{}, Int<0>{});
+    };
+    const CoopRun co{"BiCGStab", 3, 3 * (size_t)p.n, rmax, xl};
+    return run_chunked(s, A, x, &co, launch, ran);
 }
 
 int run_bicgstab(sgm_solver s, sgm_mat A, double *const *x, const double *const *b, sgm_pc pc)
 {
-    auto coop = [&](bool *ran) -> int {
-        int rmax = 0, H = 0;
-        bool xl = false;
-        *ran = false;
-        for (int attempt = 0; attempt < 2 && !*ran && !s->coop_retired && coop_applies(s, A, pc, &rmax, &H, &xl, true); ++attempt) {
-            SGM_TRY(run_bicg_coop(s, A, x[0], b[0], pc, rmax, H, xl, ran));
-            if (!*ran && xl) s->coop_xl_retired = true;
-            if (!xl) break;
-        }
-        return SGM_OK;
-    };
-    bool ran = false, coop_tried = false;
-    if (small_applies(s, A, pc, true)) {
-        // (one workgroup: 8.2 us per iteration at 5k stored slots, 12.9 at 20k; the cooperative kernel ~10.7 whatever the size)
-        const Part &p0 = A->parts[0];
-        if ((cg_small_sliced(p0) ? (int64_t)p0.n * p0.sw : p0.nnz) > 12288) {
-            coop_tried = true;
-            SGM_TRY(coop(&ran));
-            if (ran) return SGM_OK;
-        }
-        SGM_TRY(run_bicgstab_small(s, A, x[0], b[0], pc, &ran));
-        if (ran) return SGM_OK;
-    }
-    if (!coop_tried) {
-        SGM_TRY(coop(&ran));
-        if (ran) return SGM_OK;
-    }
+    bool ran = false;
+    SGM_TRY(fast_paths(s, A, x[0], b[0], pc, true, run_bicgstab_small, run_bicg_coop, &ran));
+    if (ran) return SGM_OK;
     const size_t P = s->work.size();
     const int pk = pc ? pc_kind(pc) : 0;
     Views v;
@@ -819,11 +723,7 @@ int run_bicgstab(sgm_solver s, sgm_mat A, double *const *x, const double *const 
     const bool graphs = graph_applies(s, A, pc);
     GraphBatch gb;
     for (;;) {
-        // the host looks at the stop flag once per batch (a stream synchronisation + three small copies, ~20 us): batches
-        // grow with the iterations already done -- at most an eighth of them run past the stop as early-exit kernels
-        int64_t batch = batch_max > 1 ? std::min<int64_t>(128, std::max<int64_t>(batch_max, k / 8)) : batch_max;
-        if (graphs && batch > kGraphIters) batch -= batch % kGraphIters;     // k stays on the replay grid whatever krylov_graph_after is
-        if (s->max_iter > 0) batch = std::min<int64_t>(batch, s->max_iter - k);
+        const int64_t batch = next_batch(s, k, batch_max, graphs);
         // (replays of one captured group of kGraphIters iterations once the solve has run long enough: see GraphBatch; the
         //  kernels stop on any nonzero flag, so a group needs no generations)
         if (graphs && k >= s->graph_after() && k % kGraphIters == 0 && batch >= kGraphIters &&
@@ -843,9 +743,7 @@ int run_bicgstab(sgm_solver s, sgm_mat A, double *const *x, const double *const 
     }
     if (s->hist_cap && iters >= 1 && iters <= s->hist_cap)    // res2 after the last iteration
         SGM_HIP(hipMemcpy(s->work[0].history + (iters - 1), s->work[0].res, 8, hipMemcpyDeviceToDevice));
-    s->last_iterations = iters;
-    s->res2 = res;
-    s->converged = flag;
+    store_result(s, flag, iters, res);
     return SGM_OK;
 }
 

@@ -130,7 +130,7 @@ __global__ __launch_bounds__(1024) void k_cg_small(
     if (tid == 0) { *iters = it; *res_out = res2; *flag = conv ? 1 : 0; }
 }
 
-// returns SGM_OK with *ran = false when the kernel cannot be launched here (LDS request refused)
+// *ran = false: the kernel cannot be launched here (LDS request refused)
 static int run_cg_small(sgm_solver s, sgm_mat A, double *x, const double *b, sgm_pc pc, bool *ran)
 {
     const Part &p = A->parts[0];
@@ -139,39 +139,24 @@ static int run_cg_small(sgm_solver s, sgm_mat A, double *x, const double *b, sgm
     const bool sliced = cg_small_sliced(p);
     const size_t npad = (size_t)((p.n + 1) & ~1);
     const size_t lds = ((s->seq ? 2 : 1) * npad + 16) * sizeof(double);
-    // the reference's loop has no iteration cap; a launch has one (kCgSmallChunk iterations), after which the solve
-    // continues in the next launch from r, p and res2 parked in the solver's work vectors -- the host stays in control
-    const int64_t kCgSmallChunk = s->small_chunk();
-    int flag = 0; int64_t iters = 0; double res = 0.0;
-    *ran = true;
-    for (int resume = 0;; resume = 1) {
-        int64_t it_end = iters + kCgSmallChunk;
-        if (s->max_iter > 0) it_end = std::min<int64_t>(it_end, s->max_iter);
-#define LS(R, J, S, Q)                                                                                               \
-    do {                                                                                                             \
-        if (!allow_lds((const void *)k_cg_small<R, J, S, Q>, lds)) { *ran = false; return SGM_OK; }                   \
-        hipLaunchKernelGGL((k_cg_small<R, J, S, Q>), dim3(1), dim3(1024), lds, g_rt.stream, p.n, p.sw,                \
-                           S ? reinterpret_cast<const int32_t *>(p.scode) : (const int32_t *)p.rowptr,                \
-                           S ? (const int32_t *)p.dict : (const int32_t *)p.col, S ? (const double *)p.sval : (const double *)p.val, \
-                           x, b, jac ? pc_idiag(pc, 0) : nullptr,                                                     \
-                           s->tolerance, it_end, resume, w.vec[V_R], w.vec[V_P], w.flag, w.iters, w.res, w.history,   \
-                           s->hist_cap);                                                                              \
-    } while (0)
-#define LSQ(R, J, S) do { if (s->seq) LS(R, J, S, true); else LS(R, J, S, false); } while (0)
-        if (sliced) {
-            if (p.n <= 4096) { if (jac) LSQ(4, true, true); else LSQ(4, false, true); }
-            else { if (jac) LSQ(10, true, true); else LSQ(10, false, true); }
-        } else { if (jac) LSQ(4, true, false); else LSQ(4, false, false); }
-#undef LSQ
-#undef LS
-        SGM_HIP(hipGetLastError());
-        SGM_TRY(read_state(s, &flag, &iters, &res));
-        if (flag || (s->max_iter > 0 && iters >= s->max_iter)) break;
-    }
-    s->last_iterations = iters;
-    s->res2 = res;
-    s->converged = flag;
-    return SGM_OK;
+    auto launch = [&](int64_t it_end, int resume, const CoopArgs &) {
+        auto go = [&](auto R, auto SL) {                // k_cg_small<R, jac, SL, dot_order = 1>
+            constexpr bool S = decltype(SL)::value;
+            return with_flag(jac, [&](auto J) { return with_flag(s->seq, [&](auto Q) {
+                auto *k = k_cg_small<decltype(R)::value, decltype(J)::value, S, decltype(Q)::value>;
+                if (!allow_lds((const void *)k, lds)) return false;
+                hipLaunchKernelGGL(k, dim3(1), dim3(1024), lds, g_rt.stream, p.n, p.sw,
+                                   S ? reinterpret_cast<const int32_t *>(p.scode) : (const int32_t *)p.rowptr,
+                                   S ? (const int32_t *)p.dict : (const int32_t *)p.col, S ? (const double *)p.sval : (const double *)p.val,
+                                   x, b, jac ? pc_idiag(pc, 0) : nullptr, s->tolerance, it_end, resume, w.vec[V_R], w.vec[V_P],
+                                   w.flag, w.iters, w.res, w.history, s->hist_cap);
+                return true;
+            }); });
+        };
+        if (!sliced) return go(Int<4>{}, Flag<false>{});
+        return p.n <= 4096 ? go(Int<4>{}, Flag<true>{}) : go(Int<10>{}, Flag<true>{});
+    };
+    return run_chunked(s, A, x, nullptr, launch, ran);
 }
 
 // SW > 0: the own rows' matrix entries (SW slots each) are loaded ONCE and live in registers for the whole launch (RMAX * SW
@@ -203,26 +188,27 @@ __global__ __launch_bounds__(1024) void k_cg_coop(
     double *ml = red + 32;                               // LS x RPW matrix entries (LS > 0) -- or, RL, the own rows of r
     double *rls = red + 32;
     __shared__ int32_t dl[16];
-    if (XL && (blockIdx.x & 7) != 0) return;
-    const int tid = threadIdx.x, G = XL ? (int)(gridDim.x >> 3) : (int)gridDim.x, wg = XL ? (int)(blockIdx.x >> 3) : (int)blockIdx.x;
-    const int32_t r0 = wg * RPW, r1 = min(n, r0 + RPW);
+    if (coop_idle<XL>()) return;
+    const CoopGeom g = coop_geom<RPW, XL>(n);
+    const int tid = threadIdx.x, G = g.G, wg = g.wg;
+    const int32_t r0 = g.r0, r1 = g.r1;
     if (tid < 16) dl[tid] = dict[tid];
     int h = h0;
     // all-reduce of one partial sum per workgroup (+ whatever this workgroup published before the call)
 #ifdef SGM_COOP_PROBE
     long long pacc_[16] = {0}, *pacc = pacc_, tlast = 0;
     const bool probing = wg == 0 && tid == 0;
-    auto handoff = [&](double mine, double &total) { const bool ok_ = coop_handoff(slots, h, mine, wg, G, XL, abort, spin_limit, red, lds_ok, &total, XL ? 1 : kCoopReplicas, probing ? pacc : nullptr); ++h; return ok_; };
 #else
-    auto handoff = [&](double mine, double &total) { const bool ok_ = coop_handoff(slots, h, mine, wg, G, XL, abort, spin_limit, red, lds_ok, &total, XL ? 1 : kCoopReplicas); ++h; return ok_; };
+    constexpr long long *pacc = nullptr;
+    constexpr bool probing = false;
 #endif
-    auto own_dot = [&](const double (&prod)[RMAX]) {
-        double sacc = 0.0;
-#pragma unroll
-        for (int u = 0; u < RMAX; ++u) sacc += prod[u];
-        return block_sum<BLOCK>(sacc, red);
+    auto handoff = [&](double mine, double &total) {
+        const bool ok_ = coop_handoff<1>(slots, h, mine, 0.0, wg, G, XL, abort, spin_limit, red, lds_ok, &total, nullptr, XL ? 1 : kCoopReplicas, false, probing ? pacc : nullptr);
+        ++h;
+        return ok_;
     };
-    // the halo of a vector that lives in global memory (published with sc1 stores by its owners) into pl
+    auto own_dot = [&](const double (&prod)[RMAX]) { return coop_dot<RMAX>(prod, red); };
+    // the resident matrix and the row sums: the same text as k_bicg_coop's, written out in both on purpose (sgm_coop.hpp, header comment)
     uint32_t cwr[RMAX];
     double mv[RMAX][SW > 0 ? SW : 1];
 #pragma unroll
@@ -278,13 +264,7 @@ __global__ __launch_bounds__(1024) void k_cg_coop(
         for (int u = 0; u < RMAX; ++u) q[u] = 0.0 + q[u];
     };
     // publish the first / last H own rows of z; (after the hand-off) halo rows of pl <- f(neighbour's z, old halo p)
-    auto publish = [&](const double (&zr)[RMAX]) {
-#pragma unroll
-        for (int u = 0; u < RMAX; ++u) {
-            const int32_t li = tid + u * BLOCK, i = r0 + li;
-            if (i < r1 && (li < H || i >= r1 - H)) st_pub(gz + i, zr[u], XL);
-        }
-    };
+    auto publish = [&](const double (&zr)[RMAX]) { coop_publish<RMAX>(gz, zr, g, H, XL); };
     double xr[RMAX], rr[RL ? 1 : RMAX], prod[RMAX];
     auto R = [&](int u) -> double & { return RL ? rls[tid + u * BLOCK] : rr[RL ? 0 : u]; };
     // ---- start: p = x in LDS (own rows + halo) for r = b - A x
@@ -305,7 +285,7 @@ __global__ __launch_bounds__(1024) void k_cg_coop(
     if (XL) {                                              // the proof of co-location (placement-independent hand-off)
         double total;
         const double mark = __longlong_as_double((long long)(1023 + 6 * xcc_id()) << 52);       // 64^id
-        ok = coop_handoff(slots, h, mark, wg, G, false, abort, spin_limit, red, lds_ok, &total, 1);
+        ok = coop_handoff<1>(slots, h, mark, 0.0, wg, G, false, abort, spin_limit, red, lds_ok, &total, nullptr, 1, false);
         ++h;
         if (ok && total != mark * (double)G) {
             if (tid == 0) __hip_atomic_store(abort, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -437,7 +417,7 @@ extern "C" int sgm_debug_coop_probe(long long out[16])
 }
 #endif
 
-// *ran = false: the kernel could not be launched here, or a hand-off gave up -- the caller runs the launch loop from the caller's x
+// (2 hand-offs per iteration; one exchange vector, z)
 static int run_cg_coop(sgm_solver s, sgm_mat A, double *x, const double *b, sgm_pc pc, int rmax, int H, bool xl, bool *ran)
 {
     const Part &p = A->parts[0];
@@ -448,141 +428,48 @@ static int run_cg_coop(sgm_solver s, sgm_mat A, double *x, const double *b, sgm_
     // 4 rows per thread (streamed matrix): three slots of it in LDS where they fit beside p and its halo
     const bool ls3 = !xl && rmax == 4 && (size_t)(rpw + 2 * H + 32 + 3 * rpw) * sizeof(double) <= 160 * 1024;
     const size_t lds = (size_t)(rpw + 2 * H + 32 + (ls3 ? 3 * rpw : rmax == 8 ? rpw : 0)) * sizeof(double);
-    *ran = false;
-    auto arm = [&]() -> int { return coop_arm(s, p.n); };
-    if (!s->coop_buf) {
-        if (dalloc(&s->coop_buf, (size_t)p.n + (size_t)kCoopSlotDoubles + 64) != SGM_OK) return SGM_OK;
-        SGM_TRY(arm());
-    }
-    double *gz = s->coop_buf, *slots = gz + p.n;
-    int *abortw = reinterpret_cast<int *>(slots + (size_t)kCoopSlotDoubles);
-    int flag = 0; int64_t iters = 0; double res = 0.0;
-    // the caller's x, kept until the first launch has ended: a hand-off that gives up at the LAST join of a launch can leave
-    // workgroups that passed it storing their rows of x while the others leave theirs -- an aborted first launch hands the
-    // launch loop the caller's x again, not that mixture
-    if (!s->x_backup) SGM_TRY(dalloc(&s->x_backup, (size_t)p.n + 2));
-    SGM_HIP(hipMemcpyAsync(s->x_backup, x, (size_t)p.n * 8, hipMemcpyDeviceToDevice, g_rt.stream));
-    for (int resume = 0;; resume = 1) {
-        int64_t it_end = iters + s->small_chunk();
-        if (s->max_iter > 0) it_end = std::min<int64_t>(it_end, s->max_iter);
-        const int spin = s->opt.coop_spin_limit > 0 ? s->opt.coop_spin_limit : kCoopSpinLimit;
-#define LC(R, J, W, X)                                                                                                 \
-    do {                                                                                                             \
-        if (!allow_lds((const void *)k_cg_coop<R, J, W, X>, lds)) return SGM_OK;                                      \
-        hipLaunchKernelGGL((k_cg_coop<R, J, W, X>), dim3(X ? 8 * G : G), dim3(1024), lds, g_rt.stream, p.n, p.sw, H, (const uint32_t *)p.scode, \
-                           (const int32_t *)p.dict, (const double *)p.sval, x, b, jac ? pc_idiag(pc, 0) : nullptr,   \
-                           s->tolerance, it_end, resume, w.vec[V_R], w.vec[V_P], gz, slots, abortw, s->coop_base & 3, spin, \
-                           w.flag, w.iters, w.res, w.history, s->hist_cap);                                           \
-    } while (0)
-#define LC5(R, J, W, X, L)                                                                                              \
-    do {                                                                                                             \
-        if (!allow_lds((const void *)k_cg_coop<R, J, W, X, L>, lds)) return SGM_OK;                                   \
-        hipLaunchKernelGGL((k_cg_coop<R, J, W, X, L>), dim3(X ? 8 * G : G), dim3(1024), lds, g_rt.stream, p.n, p.sw, H, (const uint32_t *)p.scode, \
-                           (const int32_t *)p.dict, (const double *)p.sval, x, b, jac ? pc_idiag(pc, 0) : nullptr,   \
-                           s->tolerance, it_end, resume, w.vec[V_R], w.vec[V_P], gz, slots, abortw, s->coop_base & 3, spin, \
-                           w.flag, w.iters, w.res, w.history, s->hist_cap);                                           \
-    } while (0)
-#define LC6(R, J)                                                                                                      \
-    do {                                                                                                             \
-        if (!allow_lds((const void *)k_cg_coop<R, J, 0, false, 0, true>, lds)) return SGM_OK;                         \
-        hipLaunchKernelGGL((k_cg_coop<R, J, 0, false, 0, true>), dim3(G), dim3(1024), lds, g_rt.stream, p.n, p.sw, H, (const uint32_t *)p.scode, \
-                           (const int32_t *)p.dict, (const double *)p.sval, x, b, jac ? pc_idiag(pc, 0) : nullptr,   \
-                           s->tolerance, it_end, resume, w.vec[V_R], w.vec[V_P], gz, slots, abortw, s->coop_base & 3, spin, \
-                           w.flag, w.iters, w.res, w.history, s->hist_cap);                                           \
-    } while (0)
-#define LCJ(R, W, X) do { if (jac) LC(R, true, W, X); else LC(R, false, W, X); } while (0)
-        // the matrix in registers where RMAX * sw doubles fit beside x, r and the temporaries
-#define LCW(R, X) do { if (p.sw == 3) LCJ(R, 3, X); else if (p.sw == 5) LCJ(R, 5, X); else if (p.sw == 7) LCJ(R, 7, X); else LCJ(R, 8, X); } while (0)
-        constexpr bool stream_env = false;          // (true: never keep the matrix in registers -- measured slower wherever the registers hold it)
+    auto launch = [&](int64_t it_end, int resume, const CoopArgs &c) {
+        auto go = [&](auto R, auto W, auto X, auto L, auto RL) {          // k_cg_coop<R, jac, W, X, L, RL>
+            return with_flag(jac, [&](auto J) {
+                auto *k = k_cg_coop<decltype(R)::value, decltype(J)::value, decltype(W)::value, decltype(X)::value, decltype(L)::value, decltype(RL)::value>;
+                if (!allow_lds((const void *)k, lds)) return false;
+                hipLaunchKernelGGL(k, dim3(decltype(X)::value ? 8 * G : G), dim3(1024), lds, g_rt.stream, p.n, p.sw, H, (const uint32_t *)p.scode,
+                                   (const int32_t *)p.dict, (const double *)p.sval, x, b, jac ? pc_idiag(pc, 0) : nullptr,
+                                   s->tolerance, it_end, resume, w.vec[V_R], w.vec[V_P], c.gz, c.slots, c.abort, c.h0, c.spin,
+                                   w.flag, w.iters, w.res, w.history, s->hist_cap);
+                return true;
+            });
+        };
+        constexpr Int<0> none{};
+        constexpr Flag<false> no{};
+        // the matrix in registers where RMAX * sw doubles fit beside x, r and the temporaries: 1 or 2 rows per thread at any slice
+        // width, 3 rows (one XCD only) up to 5 slots; otherwise streamed
         // (RMAX = 4 with the matrix in registers spills 14-76 VGPRs, RMAX = 10 streamed 99-157: not instantiated)
+        auto resident = [&](auto R, auto X) { return with_slots(p.sw, [&](auto W) { return go(R, W, X, none, no); }); };
         if (xl) {
-            if (rmax == 1 && !stream_env) LCW(1, true);
-            else if (rmax == 2 && !stream_env) LCW(2, true);
-            else if (rmax == 3 && !stream_env && p.sw <= 5) { if (p.sw == 3) LCJ(3, 3, true); else LCJ(3, 5, true); }
-            else if (rmax == 1) LCJ(1, 0, true);
-            else if (rmax == 2) LCJ(2, 0, true);
-            else if (rmax == 3) LCJ(3, 0, true);
-            else LCJ(4, 0, true);
+            constexpr Flag<true> one_xcd{};
+            if (rmax == 1) return resident(Int<1>{}, one_xcd);
+            if (rmax == 2) return resident(Int<2>{}, one_xcd);
+            if (rmax == 3 && p.sw == 3) return go(Int<3>{}, Int<3>{}, one_xcd, none, no);
+            if (rmax == 3 && p.sw <= 5) return go(Int<3>{}, Int<5>{}, one_xcd, none, no);
+            if (rmax == 3) return go(Int<3>{}, none, one_xcd, none, no);
+            return go(Int<4>{}, none, one_xcd, none, no);
         }
-        else if (rmax == 1 && !stream_env) LCW(1, false);
-        else if (rmax == 2 && !stream_env) LCW(2, false);
-        else if (rmax == 1) LCJ(1, 0, false);
-        else if (rmax == 2) LCJ(2, 0, false);
-        else if (rmax == 8) { if (jac) LC6(8, true); else LC6(8, false); }
-        else if (ls3) { if (jac) LC5(4, true, 0, false, 3); else LC5(4, false, 0, false, 3); }
-        else LCJ(4, 0, false);
-#undef LCW
-#undef LCJ
-#undef LC6
-#undef LC5
-#undef LC
-        SGM_HIP(hipGetLastError());
-        int habort = 0;
-        SGM_HIP(hipMemcpyAsync(&habort, abortw, sizeof(int), hipMemcpyDeviceToHost, g_rt.stream));
-        SGM_TRY(read_state(s, &flag, &iters, &res));
-        if (habort) {
-            // a hand-off gave up (the grid was not co-resident, or the GPU is shared).  A resumed solve has moved x already:
-            // restart is only exact from the caller's x, which is put back after a first launch
-            SGM_TRY(arm());
-            if (!resume) SGM_HIP(hipMemcpyAsync(x, s->x_backup, (size_t)p.n * 8, hipMemcpyDeviceToDevice, g_rt.stream));
-            if (xl) {
-                // (the participants were not dealt to one XCD, or one of them never started: the all-CU variant has its turn)
-                s->coop_xl_retired = true;
-            } else {
-                fprintf(stderr, "[sigma_hip] cooperative CG gave up waiting for a workgroup (grid not co-resident / shared GPU?): "
-                                "this solver takes the launch loop from now on\n");
-                s->coop_retired = true;
-            }
-            if (resume) return fail(SGM_ERR_HIP, "cooperative CG aborted in a continued launch");
-            return SGM_OK;
-        }
-        // hand-offs this launch made: 2 per iteration (+ 1 at the start of a fresh solve, + 1 for the XCD-local variant's proof
-        // of co-location); only their count mod 4 matters
-        s->coop_base = (int)((s->coop_base + 2 * (iters - (resume ? s->coop_iters0 : 0)) + (resume ? 0 : 1) + (xl ? 1 : 0)) & 3);
-        s->coop_iters0 = iters;
-        if (flag || (s->max_iter > 0 && iters >= s->max_iter)) break;
-    }
-    *ran = true;
-    s->last_iterations = iters;
-    s->res2 = res;
-    s->converged = flag;
-    if (trace_on())
-        fprintf(stderr, "[sigma_hip] cg: one cooperative launch per %lld iterations, %s, %d workgroups x %lld rows\n", (long long)s->small_chunk(),
-                xl ? "on one XCD" : "all CUs", G, (long long)rpw);
-    return SGM_OK;
+        if (rmax == 1) return resident(Int<1>{}, no);
+        if (rmax == 2) return resident(Int<2>{}, no);
+        if (rmax == 8) return go(Int<8>{}, none, no, none, Flag<true>{});          // r in LDS
+        if (ls3) return go(Int<4>{}, none, no, Int<3>{}, no);
+        return go(Int<4>{}, none, no, none, no);
+    };
+    const CoopRun co{"CG", 2, (size_t)p.n, rmax, xl};
+    return run_chunked(s, A, x, &co, launch, ran);
 }
 
 int run_cg(sgm_solver s, sgm_mat A, double *const *x, const double *const *b, sgm_pc pc)
 {
-    auto coop = [&](bool *ran) -> int {
-        int rmax = 0, H = 0;
-        bool xl = false;
-        *ran = false;
-        for (int attempt = 0; attempt < 2 && !*ran && !s->coop_retired && coop_applies(s, A, pc, &rmax, &H, &xl); ++attempt) {
-            SGM_TRY(run_cg_coop(s, A, x[0], b[0], pc, rmax, H, xl, ran));
-            if (!*ran && xl) s->coop_xl_retired = true;
-            if (!xl) break;                                  // (the XCD-local variant stood down: once more with all CUs)
-        }
-        return SGM_OK;
-    };
-    bool ran = false, coop_tried = false;
-    if (small_applies(s, A, pc, false)) {
-        // one workgroup takes ~1.5 us + 0.22 us per 1000 stored slots per iteration, a few workgroups of one XCD ~5 us whatever
-        // the size (round 4: tridiagonal n = 1e4 9.9 vs 5.0 us): the cooperative kernel first where it applies (>= 2048 rows)
-        // and the system has more than 12288 slots
-        const Part &p0 = A->parts[0];
-        if ((cg_small_sliced(p0) ? (int64_t)p0.n * p0.sw : p0.nnz) > 12288) {
-            coop_tried = true;
-            SGM_TRY(coop(&ran));
-            if (ran) return SGM_OK;
-        }
-        SGM_TRY(run_cg_small(s, A, x[0], b[0], pc, &ran));
-        if (ran) return SGM_OK;
-    }
-    if (!coop_tried) {
-        SGM_TRY(coop(&ran));
-        if (ran) return SGM_OK;
-    }
+    bool ran = false;
+    SGM_TRY(fast_paths(s, A, x[0], b[0], pc, false, run_cg_small, run_cg_coop, &ran));
+    if (ran) return SGM_OK;
     const size_t P = s->work.size();
     const int pk = pc ? pc_kind(pc) : 0;
     Views v;
@@ -704,11 +591,7 @@ int run_cg(sgm_solver s, sgm_mat A, double *const *x, const double *const *b, sg
     const bool graphs = graph_applies(s, A, pc);
     GraphBatch gb;
     for (;;) {
-        // the host looks at the stop flag once per batch (a stream synchronisation + three small copies, ~20 us): batches
-        // grow with the iterations already done -- at most an eighth of them run past the stop as early-exit kernels
-        int64_t batch = batch_max > 1 ? std::min<int64_t>(128, std::max<int64_t>(batch_max, k / 8)) : batch_max;
-        if (graphs && batch > kGraphIters) batch -= batch % kGraphIters;     // k stays on the replay grid whatever krylov_graph_after is
-        if (s->max_iter > 0) batch = std::min<int64_t>(batch, s->max_iter - k);
+        const int64_t batch = next_batch(s, k, batch_max, graphs);
         // a solve that has run graph_after() iterations goes on as replays of one captured group of kGraphIters (k is
         // a multiple of it here: the parity of the r.r slots repeats)
         if (graphs && k >= s->graph_after() && k % kGraphIters == 0 && batch >= kGraphIters &&
@@ -724,9 +607,7 @@ int run_cg(sgm_solver s, sgm_mat A, double *const *x, const double *const *b, sg
         SGM_TRY(read_state(s, &flag, &iters, &res));
         if (flag || s->aborted || (s->max_iter > 0 && k >= s->max_iter)) break;
     }
-    s->last_iterations = iters;
-    s->res2 = res;
-    s->converged = flag;
+    store_result(s, flag, iters, res);
     return SGM_OK;
 }
 

@@ -1,8 +1,18 @@
 // Shared by sgm_cg.hip and sgm_bicgstab.hip: what the one-workgroup and the cooperative (one launch, up to 256 workgroups)
-// solvers of small and mid-sized systems are made of -- the row sums out of LDS, the block dots in both orders, the grid-wide
-// hand-offs, and the rules that decide when these kernels apply.
+// solvers of small and mid-sized systems are made of.  Device: the one-workgroup kernels' row sums out of LDS and block dots in
+// both orders; the cooperative kernels' grid-wide hand-off (one or two scalars), workgroup geometry, publishing of boundary
+// rows and block dots.  Host: the rules that decide when these kernels apply, the driver that runs a solve as launches of
+// bounded length (run_chunked), run-time values as template arguments, and the order of the fast paths.
+// NOT here, on purpose: the cooperative kernels' matrix load, row sums, halo index arithmetic and proof of co-location.
+// k_cg_coop and k_bicg_coop each write them out, with the same text: both kernels sit at 128 VGPRs, and as shared functions
+// the first three moved spills (8 more bytes of scratch in 1 k_cg_coop and up to 18 k_bicg_coop kernels) and the proof changed
+// the text of every one-XCD kernel; with them written out every kernel compiles to the text it had before this header
+// held any device code of theirs (profiles/krylov_dedupe/README.md).
 #pragma once
 #include "sgm_krylov.hpp"
+
+#include <cctype>
+#include <string>
 
 namespace sgm {
 
@@ -221,13 +231,19 @@ static __device__ long long g_coop_probe[16];
 #else
 #define PROBE_T(k) do { } while (0)
 #endif
-__device__ inline bool coop_handoff(double *slots /* replicas x 4 x 256 */, int h, double mine, int wg, int G, bool l2, int *abort, int spin_limit, double *red,
-                                    int *lds_ok, double *sum_out, int reps, long long *pacc = nullptr, bool second_region = false)
+// NS scalars per hand-off (1, or 2: BiCGStab's t.s and t.t, r.r and r0.r): the second one travels through a slot region of its
+// own, kCoopSecond doubles further on.  A kernel that ever carries two passes both_regions = true to EVERY hand-off it makes,
+// so that both regions' sets are re-armed two hand-offs ahead whichever kind those hand-offs are.
+template <int NS>
+__device__ inline bool coop_handoff(double *slots /* replicas x 4 x 256, twice */, int h, double mine_a, double mine_b, int wg, int G, bool l2, int *abort,
+                                    int spin_limit, double *red /* 16 doubles per scalar */, int *lds_ok, double *sum_a, double *sum_b, int reps,
+                                    bool both_regions, long long *pacc = nullptr)
 {
+    static_assert(NS == 1 || NS == 2, "one or two scalars");
     // (reps = 1, the one-XCD variant: copy 0 only, for its proof of co-location too -- at most 32 pollers)
     const int my_rep = reps == 1 ? 0 : (xcc_id() & (kCoopReplicas - 1));
 #ifdef SGM_COOP_PROBE
-    const bool probing = pacc != nullptr;
+    const bool probing = NS == 1 && pacc != nullptr;
     long long tlast = probing ? wall_clock64() : 0;
 #endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // this wave's sc1 stores (boundary rows) have left
@@ -236,17 +252,21 @@ __device__ inline bool coop_handoff(double *slots /* replicas x 4 x 256 */, int 
     const int tid = threadIdx.x;
     double *set = slots + (h & 3) * 256;
     if (tid == 0) *lds_ok = 1;
-    if (tid < reps) st_pub(set + tid * kCoopRepStride + wg, mine, l2);
-    double v = 0.0;
+    if (tid < reps) {
+        st_pub(set + tid * kCoopRepStride + wg, mine_a, l2);
+        if (NS == 2) st_pub(set + kCoopSecond + tid * kCoopRepStride + wg, mine_b, l2);
+    }
+    double va = 0.0, vb = 0.0;
     int ok = 1;
     if (tid < G) {
         int spins = 0;
         for (;;) {
-            v = ld_sc1(set + my_rep * kCoopRepStride + tid);
-            if (__double_as_longlong(v) != (long long)kCoopPoison) break;
+            va = ld_sc1(set + my_rep * kCoopRepStride + tid);
+            if (NS == 2) vb = ld_sc1(set + kCoopSecond + my_rep * kCoopRepStride + tid);
+            if (__double_as_longlong(va) != (long long)kCoopPoison && (NS == 1 || __double_as_longlong(vb) != (long long)kCoopPoison)) break;
             if (++spins > spin_limit || ((spins & 31) == 0 && __hip_atomic_load(abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
                 __hip_atomic_store(abort, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                ok = 0; v = 0.0;
+                ok = 0; va = 0.0; vb = 0.0;
                 break;
             }
             __builtin_amdgcn_s_sleep(1);
@@ -256,58 +276,64 @@ __device__ inline bool coop_handoff(double *slots /* replicas x 4 x 256 */, int 
     __syncthreads();                                         // (lds_ok = 1 is visible before anyone clears it)
     PROBE_T(10);
     if (!ok) *lds_ok = 0;
-    const double ssum = block_sum<1024>(v, red);             // (its barriers publish lds_ok)
+    double sa, sb = 0.0;
+    if constexpr (NS == 1) sa = block_sum<1024>(va, red);             // (its barriers publish lds_ok)
+    else block_sum2<1024>(va, vb, red, sa, sb);
     PROBE_T(11);
     if (tid < reps) {
         st_pub(slots + ((h + 2) & 3) * 256 + tid * kCoopRepStride + wg, __longlong_as_double((long long)kCoopPoison), l2);
-        if (second_region) st_pub(slots + kCoopSecond + ((h + 2) & 3) * 256 + tid * kCoopRepStride + wg, __longlong_as_double((long long)kCoopPoison), l2);
-    }
-    *sum_out = ssum;
-    return *lds_ok != 0;
-}
-// The same hand-off carrying TWO scalars (BiCGStab's t.s and t.t, r.r and r0.r): the second one through a slot region of its
-// own, kCoopSecond doubles further on.  A kernel that uses it passes second_region = true to EVERY hand-off it makes, so that
-// both regions' sets are re-armed two hand-offs ahead whichever kind those hand-offs are.
-__device__ inline bool coop_handoff2(double *slots, int h, double mine_a, double mine_b, int wg, int G, bool l2, int *abort, int spin_limit, double *red,
-                                     int *lds_ok, double *sum_a, double *sum_b, int reps)
-{
-    const int my_rep = reps == 1 ? 0 : (xcc_id() & (kCoopReplicas - 1));
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    const int tid = threadIdx.x;
-    double *set = slots + (h & 3) * 256;
-    if (tid == 0) *lds_ok = 1;
-    if (tid < reps) {
-        st_pub(set + tid * kCoopRepStride + wg, mine_a, l2);
-        st_pub(set + kCoopSecond + tid * kCoopRepStride + wg, mine_b, l2);
-    }
-    double va = 0.0, vb = 0.0;
-    int ok = 1;
-    if (tid < G) {
-        int spins = 0;
-        for (;;) {
-            va = ld_sc1(set + my_rep * kCoopRepStride + tid);
-            vb = ld_sc1(set + kCoopSecond + my_rep * kCoopRepStride + tid);
-            if (__double_as_longlong(va) != (long long)kCoopPoison && __double_as_longlong(vb) != (long long)kCoopPoison) break;
-            if (++spins > spin_limit || ((spins & 31) == 0 && __hip_atomic_load(abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
-                __hip_atomic_store(abort, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                ok = 0; va = 0.0; vb = 0.0;
-                break;
-            }
-            __builtin_amdgcn_s_sleep(1);
-        }
-    }
-    __syncthreads();
-    if (!ok) *lds_ok = 0;
-    double sa, sb;
-    block_sum2<1024>(va, vb, red, sa, sb);                   // (red: 32 doubles here; its barriers publish lds_ok)
-    if (tid < reps) {
-        st_pub(slots + ((h + 2) & 3) * 256 + tid * kCoopRepStride + wg, __longlong_as_double((long long)kCoopPoison), l2);
-        st_pub(slots + kCoopSecond + ((h + 2) & 3) * 256 + tid * kCoopRepStride + wg, __longlong_as_double((long long)kCoopPoison), l2);
+        if (NS == 2 || both_regions) st_pub(slots + kCoopSecond + ((h + 2) & 3) * 256 + tid * kCoopRepStride + wg, __longlong_as_double((long long)kCoopPoison), l2);
     }
     *sum_a = sa;
-    *sum_b = sb;
+    if (NS == 2) *sum_b = sb;
     return *lds_ok != 0;
+}
+
+// ---- what k_cg_coop and k_bicg_coop are made of besides the hand-offs (1024 threads, RMAX rows per thread: tid + u * 1024) ----
+// The workgroup's place in the launch.  XL (one XCD): the grid is 8 x G workgroups, of which those with blockIdx % 8 == 0 --
+// dealt to ONE XCD by the round-robin dispatch -- take part; the others are idle and leave at once, before anything else.
+template <bool XL> __device__ inline bool coop_idle() { return XL && (blockIdx.x & 7) != 0; }
+struct CoopGeom {
+    int G, wg;                  // participants, this workgroup's number among them
+    int32_t r0, r1;             // its rows
+};
+template <int RPW, bool XL>
+__device__ inline CoopGeom coop_geom(int32_t n)
+{
+    CoopGeom g;
+    g.G = XL ? (int)(gridDim.x >> 3) : (int)gridDim.x;
+    g.wg = XL ? (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+    g.r0 = g.wg * RPW;
+    g.r1 = min(n, g.r0 + RPW);
+    return g;
+}
+// the first / last H own rows of an own-row vector to an exchange vector (what the neighbours' halos are formed from)
+template <int RMAX>
+__device__ inline void coop_publish(double *dst, const double (&w)[RMAX], const CoopGeom &g, int32_t H, bool l2)
+{
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int u = 0; u < RMAX; ++u) {
+        const int32_t li = tid + u * 1024, i = g.r0 + li;
+        if (i < g.r1 && (li < H || i >= g.r1 - H)) st_pub(dst + i, w[u], l2);
+    }
+}
+// this workgroup's part of a dot product (prod: 0.0 on the rows beyond r1), or of two that share their barriers
+template <int RMAX>
+__device__ inline double coop_dot(const double (&prod)[RMAX], double *red)
+{
+    double sacc = 0.0;
+#pragma unroll
+    for (int u = 0; u < RMAX; ++u) sacc += prod[u];
+    return block_sum<1024>(sacc, red);
+}
+template <int RMAX>
+__device__ inline void coop_dot2(const double (&pa)[RMAX], const double (&pb)[RMAX], double *red, double &sa, double &sb)
+{
+    double a = 0.0, c = 0.0;
+#pragma unroll
+    for (int u = 0; u < RMAX; ++u) { a += pa[u]; c += pb[u]; }
+    block_sum2<1024>(a, c, red, sa, sb);
 }
 constexpr int kCoopSpinLimit = 1 << 19;       // polls (about a microsecond each) before a hand-off gives up
 // sliced stencil matrix on one GPU, plain or Jacobi, tree-order dots, beyond the one-workgroup kernel and up to 256 workgroups
@@ -367,6 +393,125 @@ static int coop_arm(sgm_solver s, size_t n /* doubles of exchange vectors in fro
     SGM_HIP(hipMemsetAsync(s->coop_buf + n + (size_t)kCoopSlotDoubles, 0, 64, g_rt.stream));
     SGM_HIP(hipStreamSynchronize(g_rt.stream));
     s->coop_base = 0;
+    return SGM_OK;
+}
+
+// ---- host: one driver for the four fast-path runners, kernel selection, the order small / cooperative / loop ---------------
+// Run-time values as template arguments: f is called once with a std::integral_constant (sgm_spmv_select.hpp: with_flags).
+template <int V> using Int = std::integral_constant<int, V>;
+template <bool V> using Flag = std::integral_constant<bool, V>;
+template <class F> static bool with_flag(bool v, F &&f) { return v ? f(Flag<true>{}) : f(Flag<false>{}); }
+// the slice widths with a matrix-in-registers kernel of their own: 3, 5, 7; everything else up to 8 takes the 8-slot one
+template <class F> static bool with_slots(int sw, F &&f) { return sw == 3 ? f(Int<3>{}) : sw == 5 ? f(Int<5>{}) : sw == 7 ? f(Int<7>{}) : f(Int<8>{}); }
+
+// What a cooperative solver tells the driver, and what the driver hands its launches
+struct CoopRun {
+    const char *name;           // "CG" / "BiCGStab": the two messages, and in lower case the trace line
+    int per_iter;               // hand-offs per iteration (+ 1 at the start of a fresh solve, + 1 for the one-XCD form's proof)
+    size_t nx;                  // doubles of exchange vectors in front of the slots
+    int rmax; bool xl;
+};
+struct CoopArgs { double *gz = nullptr, *slots = nullptr; int *abort = nullptr; int h0 = 0, spin = 0; };
+// A solve as launches of at most small_chunk() iterations: the reference's loop has no iteration cap; a launch has one, after
+// which the solve continues in the next launch from the vectors and scalars the kernel parked in the solver's work area -- the
+// host stays in control.  launch(it_end, resume, args) -> false: the kernel cannot be launched here (LDS request refused).
+// *ran = false: that, or (co) a hand-off gave up -- the caller runs the next path from the caller's x.
+template <class Launch>
+static int run_chunked(sgm_solver s, sgm_mat A, double *x, const CoopRun *co, Launch &&launch, bool *ran)
+{
+    const size_t n = (size_t)A->parts[0].n;
+    CoopArgs c;
+    *ran = false;
+    if (co) {
+        if (!s->coop_buf) {
+            if (dalloc(&s->coop_buf, co->nx + (size_t)kCoopSlotDoubles + 64) != SGM_OK) return SGM_OK;
+            SGM_TRY(coop_arm(s, co->nx));
+        }
+        c.gz = s->coop_buf; c.slots = c.gz + co->nx;
+        c.abort = reinterpret_cast<int *>(c.slots + (size_t)kCoopSlotDoubles);
+        c.spin = s->opt.coop_spin_limit > 0 ? s->opt.coop_spin_limit : kCoopSpinLimit;
+        // the caller's x, kept until the first launch has ended: a hand-off that gives up at the LAST join of a launch can leave
+        // workgroups that passed it storing their rows of x while the others leave theirs -- an aborted first launch hands the
+        // launch loop the caller's x again, not that mixture
+        if (!s->x_backup) SGM_TRY(dalloc(&s->x_backup, n + 2));
+        SGM_HIP(hipMemcpyAsync(s->x_backup, x, n * 8, hipMemcpyDeviceToDevice, g_rt.stream));
+    }
+    int flag = 0; int64_t iters = 0; double res = 0.0;
+    for (int resume = 0;; resume = 1) {
+        int64_t it_end = iters + s->small_chunk();
+        if (s->max_iter > 0) it_end = std::min<int64_t>(it_end, s->max_iter);
+        c.h0 = s->coop_base & 3;
+        if (!launch(it_end, resume, c)) return SGM_OK;
+        SGM_HIP(hipGetLastError());
+        int habort = 0;
+        if (co) SGM_HIP(hipMemcpyAsync(&habort, c.abort, sizeof(int), hipMemcpyDeviceToHost, g_rt.stream));
+        SGM_TRY(read_state(s, &flag, &iters, &res));
+        if (habort) {
+            // a hand-off gave up (the grid was not co-resident, or the GPU is shared).  A resumed solve has moved x already:
+            // restart is only exact from the caller's x, which is put back after a first launch
+            SGM_TRY(coop_arm(s, co->nx));
+            if (!resume) SGM_HIP(hipMemcpyAsync(x, s->x_backup, n * 8, hipMemcpyDeviceToDevice, g_rt.stream));
+            if (co->xl) {
+                // (the participants were not dealt to one XCD, or one of them never started: the all-CU variant has its turn)
+                s->coop_xl_retired = true;
+            } else {
+                fprintf(stderr, "[sigma_hip] cooperative %s gave up waiting for a workgroup (grid not co-resident / shared GPU?): "
+                                "this solver takes the launch loop from now on\n", co->name);
+                s->coop_retired = true;
+            }
+            if (resume) return fail(SGM_ERR_HIP, "cooperative %s aborted in a continued launch", co->name);
+            return SGM_OK;
+        }
+        if (co) {           // hand-offs this launch made; only their count mod 4 matters
+            s->coop_base = (int)((s->coop_base + co->per_iter * (iters - (resume ? s->coop_iters0 : 0)) + (resume ? 0 : 1) + (co->xl ? 1 : 0)) & 3);
+            s->coop_iters0 = iters;
+        }
+        if (flag || (s->max_iter > 0 && iters >= s->max_iter)) break;
+    }
+    *ran = true;
+    store_result(s, flag, iters, res);
+    if (co && trace_on()) {
+        std::string lower(co->name);
+        for (char &ch : lower) ch = (char)std::tolower((unsigned char)ch);
+        const int64_t rpw = (int64_t)co->rmax * 1024;
+        fprintf(stderr, "[sigma_hip] %s: one cooperative launch per %lld iterations, %s, %d workgroups x %lld rows\n", lower.c_str(),
+                (long long)s->small_chunk(), co->xl ? "on one XCD" : "all CUs", (int)((n + rpw - 1) / rpw), (long long)rpw);
+    }
+    return SGM_OK;
+}
+
+// The fast paths in front of a launch loop, in their order.  One workgroup takes ~1.5 us + 0.22 us per 1000 stored slots per
+// CG iteration (BiCGStab: 8.2 us at 5k slots, 12.9 at 20k), a few workgroups of one XCD ~5 us (BiCGStab ~10.7) whatever the
+// size (round 4: tridiagonal n = 1e4 9.9 vs 5.0 us): the cooperative kernel first where it applies (>= 2048 rows) and the
+// system has more than 12288 slots, then one workgroup, then the cooperative kernel if it has not had its turn.
+// run_small(s, A, x, b, pc, ran), run_coop(s, A, x, b, pc, rmax, H, xl, ran); *ran = false: the caller runs its launch loop.
+template <class Small, class Coop>
+static int fast_paths(sgm_solver s, sgm_mat A, double *x, const double *b, sgm_pc pc, bool bicg, Small run_small, Coop run_coop, bool *ran)
+{
+    auto coop = [&]() -> int {
+        int rmax = 0, H = 0;
+        bool xl = false;
+        *ran = false;
+        for (int attempt = 0; attempt < 2 && !*ran && !s->coop_retired && coop_applies(s, A, pc, &rmax, &H, &xl, bicg); ++attempt) {
+            SGM_TRY(run_coop(s, A, x, b, pc, rmax, H, xl, ran));
+            if (!*ran && xl) s->coop_xl_retired = true;
+            if (!xl) break;                                  // (the XCD-local variant stood down: once more with all CUs)
+        }
+        return SGM_OK;
+    };
+    bool coop_tried = false;
+    *ran = false;
+    if (small_applies(s, A, pc, bicg)) {
+        const Part &p0 = A->parts[0];
+        if ((cg_small_sliced(p0) ? (int64_t)p0.n * p0.sw : p0.nnz) > 12288) {
+            coop_tried = true;
+            SGM_TRY(coop());
+            if (*ran) return SGM_OK;
+        }
+        SGM_TRY(run_small(s, A, x, b, pc, ran));
+        if (*ran) return SGM_OK;
+    }
+    if (!coop_tried) SGM_TRY(coop());
     return SGM_OK;
 }
 

@@ -475,9 +475,7 @@ int run_gmres(sgm_solver s, sgm_mat A, double *const *x, const double *const *b,
         SGM_TRY(read_state(s, &flag, &iters, &res));
         if (flag || s->aborted || (s->max_iter > 0 && done_steps >= s->max_iter)) break;
     }
-    s->last_iterations = iters;
-    s->res2 = res;
-    s->converged = flag;
+    store_result(s, flag, iters, res);
     return SGM_OK;
 }
 

@@ -516,6 +516,24 @@ struct GraphBatch {
     }
 };
 
+// Iterations of the next batch of a launch loop that has run k: the host looks at the stop flag once per batch (a stream
+// synchronisation + three small copies, ~20 us), so batches grow with the iterations already done -- at most an eighth of
+// them run past the stop as early-exit kernels.  `graphs`: k stays on the replay grid whatever krylov_graph_after is.
+static inline int64_t next_batch(sgm_solver s, int64_t k, int64_t batch_max, bool graphs)
+{
+    int64_t batch = batch_max > 1 ? std::min<int64_t>(128, std::max<int64_t>(batch_max, k / 8)) : batch_max;
+    if (graphs && batch > kGraphIters) batch -= batch % kGraphIters;
+    if (s->max_iter > 0) batch = std::min<int64_t>(batch, s->max_iter - k);
+    return batch;
+}
+// what every loop leaves on the solver object when it ends
+static inline void store_result(sgm_solver s, int flag, int64_t iters, double res)
+{
+    s->last_iterations = iters;
+    s->res2 = res;
+    s->converged = flag;
+}
+
 int num_work_vectors(int kind);
 void free_work(sgm_solver s);
 // ScalarRef of partial array k on part ip / the array itself

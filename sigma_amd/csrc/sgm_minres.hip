@@ -265,8 +265,7 @@ int run_minres(sgm_solver s, sgm_mat A, double *const *x, const double *const *b
     };
     for (;;) {
         // the host looks at the stop flag once per batch; batches grow with the steps already done (run_cg)
-        int64_t batch = batch_max > 1 ? std::min<int64_t>(128, std::max<int64_t>(batch_max, k / 8)) : batch_max;
-        if (s->max_iter > 0) batch = std::min<int64_t>(batch, s->max_iter - k);
+        const int64_t batch = next_batch(s, k, batch_max, false);
         if (batch > 0) hipLaunchKernelGGL(k_flag_norm, dim3(1), dim3(64), 0, g_rt.stream, w.flag);
         for (int64_t j = 0; j < batch; ++j) SGM_TRY(enqueue_iter(k + j, (int)j + 1));
         k += batch;
@@ -277,9 +276,7 @@ int run_minres(sgm_solver s, sgm_mat A, double *const *x, const double *const *b
     int32_t failed = 0;
     SGM_HIP(hipMemcpy(&failed, &w.minres->fail, sizeof(int32_t), hipMemcpyDeviceToHost));
     s->breakdown = failed;
-    s->last_iterations = iters;
-    s->res2 = res;
-    s->converged = flag && !failed;
+    store_result(s, flag && !failed, iters, res);
     return SGM_OK;
 }
 

@@ -382,3 +382,147 @@ def test_one_solver_handle_serves_matrices_of_one_size_and_different_stencils(or
                 slack = 1 if kind == "cg" else max(3, itr // 10)
                 assert s.converged and abs(s.last_iterations - itr) <= slack, (kind, order, again, name, s.last_iterations, itr)
                 assert np.abs(u - ur).max() <= 1e-8 * np.abs(ur).max(), (kind, order, again, name)
+
+
+# ---- every instantiated rows-per-thread variant on systems of a few thousand rows ------------------------------------------
+def _banded(n, entries):
+    """CSR arrays (1-based) of the matrix with value v on offset d for (d, v) in `entries`"""
+    rows = np.arange(n)
+    keep = np.array([(rows + d >= 0) & (rows + d < n) for d, _ in entries]).T
+    cols = np.array([rows + d + 1 for d, _ in entries]).T
+    vals = np.tile(np.array([v for _, v in entries], float), (n, 1))
+    ptr = np.concatenate([[1], 1 + np.cumsum(keep.sum(axis=1))]).astype(np.int32)
+    return ptr, cols[keep].astype(np.int32), vals[keep]
+
+
+# name -> (rows, slots per row, largest |offset|, builder).  All have >= 2048 rows and > 12288 stored slots: the cooperative
+# kernel comes before the one-workgroup one (fast_paths, sgm_coop.hpp).
+_SMALL_SHAPES = {
+    "tridiagonal 4099 (slice width 3; a three-row tail in the last workgroup at 4 rows per thread)":
+        (4099, 3, 1, lambda: P.tridiag_csr(4099, 2.5, -1.0, -1.0)),
+    "5-point 64 x 41": (64 * 41, 5, 64, lambda: P.poisson2d_csr(64, 41)),
+    "5-point 64 x 65": (64 * 65, 5, 64, lambda: P.poisson2d_csr(64, 65)),
+    "5-point 96 x 86 (more than 8192 rows: a neighbour at 8 rows per thread)": (96 * 86, 5, 96, lambda: P.poisson2d_csr(96, 86)),
+    "7-point 13^3 (halo of 170 rows)": (13 ** 3, 7, 169, lambda: P.laplace3d_csr(13, 13, 13)),
+    "six slots per row, one an explicit 0.0 (no kernel of that width: the 8-slot one)":
+        (4200, 6, 3, lambda: _banded(4200, [(-3, -1.0), (-1, -1.0), (0, 4.5), (1, -1.0), (2, 0.0), (3, -1.0)])),
+}
+_PINS = {"cg": (1, 2, 4, 8), "bicgstab": (1, 2, 4)}          # rows per thread option cg_coop_variant accepts for the solver
+
+
+def _coop_plan(n, reach, bicg, variant, num_cu=256):
+    """coop_applies (sgm_coop.hpp) restated: (one XCD?, rows per thread, workgroups), or None where it refuses"""
+    H = (reach + 1) & ~1
+    force, xl_off = variant & 15, variant & 16
+    if n < 2048:
+        return None
+    if not xl_off and num_cu >= 64:
+        for r in (1, 2, 3, 4):
+            if (r != force) if force else (r == 4):
+                continue
+            if bicg and (r == 3 or (r != 1 and not force)):
+                continue
+            rpw = r * 1024
+            G = -(-n // rpw)
+            if G <= min(32, num_cu // 8) and (rpw + (4 if bicg else 2) * H + 48 + (2 * rpw if bicg and r >= 2 else 0)) * 8 <= 160 * 1024:
+                return True, r, G
+    for r in (1, 2, 4, 8):
+        if (force and r != force) or (r == 8 and bicg):
+            continue
+        rpw = r * 1024
+        G = -(-n // rpw)
+        extra = 2 * rpw if bicg and r >= 2 else rpw if r == 8 else 0
+        if G <= min(256, num_cu) and (rpw + (4 if bicg else 2) * H + 48 + extra) * 8 <= 160 * 1024:
+            return False, r, G
+    return None
+
+
+_SMALL_GRID = [(kind, shape, jac, pin + bit16) for kind in ("cg", "bicgstab") for shape in _SMALL_SHAPES for jac in (False, True)
+               for pin in _PINS[kind] for bit16 in (0, 16)]
+# a refused pin is skipped by name below; on the 256 CUs of an MI355X that must stay under a fifth of the grid
+assert 5 * sum(_coop_plan(_SMALL_SHAPES[sh][0], _SMALL_SHAPES[sh][2], k == "bicgstab", v) is None for k, sh, _, v in _SMALL_GRID) < len(_SMALL_GRID)
+
+
+def _small_shapes_child():
+    """(child process, SGM_TRACE set) every case of _SMALL_GRID beside the launch loop and beside itself cut into launches of
+    7 iterations; one JSON line per case on stdout, a marker per case on stderr in front of the library's trace line"""
+    import json
+    import torch
+    num_cu = torch.cuda.get_device_properties(0).multi_processor_count
+    sg.init(0)
+    loops = {}
+    for kind, shape, jac, variant in _SMALL_GRID:
+        n, _, reach, make = _SMALL_SHAPES[shape]
+        small = "cg_small" if kind == "cg" else "bicgstab_small"
+        ptr, node, val = make()
+        if kind == "bicgstab":
+            val = _nonsymmetric(ptr, node, val)
+        H = sg.csr_matrix(n, n, ptr, node, val)
+        b = np.sin(0.01 * np.arange(1, n + 1)) + 0.5
+
+        def run(opts):
+            pc = None
+            if jac:
+                pc = sg.jacobi(); pc.setup(H)
+            s = (sg.cg if kind == "cg" else sg.bicgstab)(1e-9)
+            s.set_history(100000)
+            for k, v in opts:
+                s.set_option(k, v)
+            s.setup(H)
+            u = np.full(n, 0.25)
+            s.solve(H, u, b, pc)
+            return u, int(s.iterations), np.array(s.history), bool(s.converged)
+
+        if (kind, shape, jac) not in loops:             # the launch loop, once per matrix
+            loops[kind, shape, jac] = run([(small, 0)])
+        ul, il, hl, cl = loops[kind, shape, jac]
+        plan = _coop_plan(n, reach, kind == "bicgstab", variant, num_cu)
+        out = {"id": [kind, shape, jac, variant], "kernel": H.kernel, "plan": plan, "num_cu": num_cu}
+        if plan is not None:
+            print("CASE %s" % json.dumps(out["id"]), file=sys.stderr, flush=True)
+            u, it, h, c = run([("cg_coop_variant", variant)])
+            u7, it7, h7, _ = run([("cg_coop_variant", variant), (small, 7)])
+            k = min(len(h), len(hl), 50 if kind == "cg" else 20)
+            out.update(iters=it, loop_iters=il, converged=c and cl, k=k, hist_err=float(np.abs(h[:k] - hl[:k]).max() / hl[:k].max()),
+                       x_err=float(np.abs(u - ul).max() / np.abs(ul).max()),
+                       chunked_same=bool(it7 == it and np.array_equal(u7, u) and np.array_equal(h7, h)))
+        print("RESULT " + json.dumps(out), flush=True)
+
+
+@pytest.fixture(scope="module")
+def small_shape_runs():
+    import json
+    env = dict(os.environ, SGM_TRACE="1", PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    p = subprocess.run([sys.executable, os.path.abspath(__file__), "--small-shapes"], capture_output=True, text=True, timeout=900, env=env)
+    assert p.returncode == 0, p.stderr[-3000:]
+    res = {json.dumps(r["id"]): r for r in (json.loads(ln[7:]) for ln in p.stdout.splitlines() if ln.startswith("RESULT "))}
+    for chunk in p.stderr.split("CASE ")[1:]:
+        head, _, rest = chunk.partition("\n")
+        res[head.strip()]["trace"] = [ln for ln in rest.splitlines() if "cooperative launch" in ln]
+    return res
+
+
+@pytest.mark.parametrize("kind,shape,jac,variant", _SMALL_GRID)
+def test_cooperative_kernels_on_small_shapes_every_rows_per_thread_pin(small_shape_runs, kind, shape, jac, variant):
+    """Systems of a few thousand rows reach every rows-per-thread variant of k_cg_coop / k_bicg_coop, on one XCD and (+ 16) on
+    all CUs, with one workgroup's tail rows, halos wider than 1024 rows' share and the 8-slot kernels: SGM_TRACE names the
+    workgroups and rows per workgroup that coop_applies' rules give, and the gates are this file's -- CG: iterations within
+    +-1 of the launch loop's, the first 50 history entries within 1e-10 relative; BiCGStab: iterations within max(3, 10 %),
+    the first 20 history entries within 1e-8; both: bit-identical when cut into launches of 7 iterations."""
+    import json
+    r = small_shape_runs[json.dumps([kind, shape, jac, variant])]
+    assert r["kernel"].startswith("k_csr_sl<"), r["kernel"]
+    if r["plan"] is None:
+        pytest.skip("cg_coop_variant = %d: coop_applies refuses %d rows per thread for %s on %d CUs" % (variant, variant & 15, shape, r["num_cu"]))
+    xl, rmax, G = r["plan"]
+    want = "%s: one cooperative launch per 50000 iterations, %s, %d workgroups x %d rows" % (kind, "on one XCD" if xl else "all CUs", G, rmax * 1024)
+    assert len(r["trace"]) == 2 and want in r["trace"][0], (want, r["trace"])
+    assert rmax == variant & 15 and r["converged"] and r["chunked_same"], r
+    if kind == "cg":
+        assert abs(r["iters"] - r["loop_iters"]) <= 1 and r["k"] == min(50, r["iters"], r["loop_iters"]) and r["hist_err"] <= 1e-10, r
+    else:
+        assert abs(r["iters"] - r["loop_iters"]) <= max(3, r["loop_iters"] // 10) and r["hist_err"] <= 1e-8 and r["x_err"] <= 1e-7, r
+
+
+if __name__ == "__main__" and sys.argv[1:] == ["--small-shapes"]:
+    _small_shapes_child()
