@@ -577,6 +577,91 @@ int sgm_lanczos(sgm_mat A, int32_t nsteps, const double *q1, double *T_host, dou
 int sgm_generalized_lanczos(sgm_mat A, sgm_mat B, sgm_solver solver_for_B, sgm_pc pc_or_null, int32_t nsteps,
                             const double *q1, double *T_host, double *Q_out, int where);
 
+/* ---- extreme eigenpairs: thick-restart Lanczos ------------------------------------------ *
+ * sgm_eigsh <- NO reference counterpart: the k smallest (which = 0, "SA") or largest (which = 1, "LA") algebraic eigenvalues
+ * of a SYMMETRIC matrix and their eigenvectors, to a residual tolerance, by thick-restart Lanczos (Wu-Simon).  Symmetry is NOT
+ * checked.  The basis (ncv + 1 columns and one work vector, 8 (ncv + 2) n bytes) never leaves HBM, Ritz vectors are formed in
+ * place on the device (sgm_basis_rotate) and the TRUE residual norms are computed and returned.  Single-GPU CSR, ELLPACK and
+ * composite matrices; row-partitioned and distributed ones are SGM_ERR_UNSUPPORTED, a non-square one SGM_ERR_DIMS;
+ * k < 1, ncv <= k, ncv > 64, ncv >= n, tol < 2^-40 (or not a number), max_restarts < 0, which not 0 or 1: SGM_ERR_BAD_ARG.
+ *
+ * The contract (this comment is its one statement: DESIGN.md 9g points here, tests/eigsh_restated.py restates it).  Every
+ * operation is rounded on its own (no FMA); `A u` is the library's product (0.0 + row sum in stored order); m = ncv; Q holds
+ * m + 1 columns q_0 .. q_m with an even leading dimension; H is the m x m projected matrix, on the host;
+ * keep = min(k + (m - k)/2, m - 1) with integer division.
+ *     q_0(i) = q1(i) / sqrt(q1.q1) ;  l = 0 ;  anorm = 0 ;  H = 0
+ *     cycle c = 0, 1, ...:
+ *       for j = l .. m-1:
+ *          w = A q_j
+ *          h_i = q_i.w, i = 0..j ;  w(:) = (..(w(:) - h_0 q_0(:)) - ..) - h_j q_j(:)    (columns ascending, every subtraction rounded)
+ *          g_i = q_i.w, i = 0..j ;  w(:) = (..(w(:) - g_0 q_0(:)) - ..) - g_j q_j(:)    (second classical Gram-Schmidt pass)
+ *          H(j,j) = h_j + g_j ;  beta_j = sqrt(w.w)
+ *          s = (j == l ? anorm : s) ; |H(j,j)| > s: s = |H(j,j)| ; beta_j > s: s = beta_j
+ *          not (beta_j > 2^-40 * s):  the cycle ends here with nc = j + 1 columns ("closed": an invariant subspace, or a NaN)
+ *          j < m-1:  H(j+1,j) = H(j,j+1) = beta_j
+ *          t = 1.0/beta_j ;  q_{j+1}(:) = w(:) * t
+ *       nc = m unless closed.  A NaN among the H(j,j), beta_j of this cycle: leave with found = 0, converged = 0
+ *       (theta, Z) = symeig(leading nc x nc block of H)    (sgm_symeig_host) ;  anorm = max(anorm, max_i |theta_i|)
+ *       order the Ritz values: ascending for SA, descending for LA, ties by index
+ *       closed:  leave with found = min(k, nc), converged = (nc >= k)            (every rho is 0)
+ *       rho_i = |beta_{m-1} * Z(m-1, i)|
+ *       rho_i <= tol * anorm for the first k in that order:  leave with found = k, converged = 1
+ *       c == max_restarts:  leave with found = k, converged = 0
+ *       Q[:, 0..keep-1] = Q[:, 0..m-1] * Z[:, first keep in that order]          (sgm_basis_rotate)
+ *       q_keep = q_m
+ *       H = 0 ;  H(i,i) = theta_i, H(keep,i) = H(i,keep) = beta_{m-1} * Z(m-1, i)   for the kept i = 0..keep-1 in that order
+ *       l = keep ;  restarts += 1
+ *     end:
+ *       V = Q[:, 0..nc-1] * Z[:, first `found` in that order]                     (sgm_basis_rotate)
+ *       lambda_i = theta_i
+ *       resid_i = sqrt(r.r), r(:) = y(:) - lambda_i * v_i(:), y = A v_i           (on the device, one product per pair)
+ * Convergence is decided by rho, the Lanczos ESTIMATE of the residual, against tol * anorm (anorm: the largest |Ritz value|
+ * seen, a lower bound of |A|_2).  resid_out is always the TRUE residual norm |A v - lambda v|_2 of the returned pair; the two
+ * are different numbers, and only rho is compared with tol.  2^-40 is a contract constant: a beta_j that small against the
+ * scale of H means the Krylov space has closed, which is why a smaller tol is refused.  A closed space with at least k Ritz
+ * pairs is convergence; with fewer, found = what there is and converged = 0.  A NaN anywhere (the matrix, q1 -- a zero q1
+ * gives 0/0 --) ends with converged = 0 and found = 0, never "converged"; the call still returns SGM_OK.
+ * Dot products: the order of every sum is a function of n alone, never of the CU count.  With G = min(1024, max(1,
+ * ceil(n / 1024))) workgroups of 256 threads, thread t of the 256 G adds the products of elements 2i, 2i+1 for i = t, t + 256 G,
+ * ... to its own accumulator, which starts at 0.0 (thread 0 then the last element of an odd n); each wave of 64 threads sums
+ * its accumulators by the butterfly v += v[lane ^ 32], ^ 16, ... ^ 1; a workgroup adds its four wave sums left to right; for
+ * G > 1 the G workgroup sums are re-reduced the same way by one workgroup: thread t adds sums t, t + 256, ... to 0.0, then the
+ * butterfly and the four wave sums.  (G = 1: MINRES's default order, minres_restated.tree_dot.)
+ * Host-device traffic: the cycle's new H(j,j) and beta_j come to the host in ONE copy per cycle -- its one synchronisation --
+ * and the selected columns of Z go back in one; within a cycle nothing waits for the host: a closed cycle raises a device
+ * flag and its remaining kernels return at once.
+ * q1: n entries (host or device per `where`).  lambda_out, resid_out: k entries on the HOST; entries from `found` on are NaN.
+ * V_out (may be NULL): n x k column-major, host or device per `where`; only the first `found` columns are written.
+ * info (host): {restarts, products with A (the residual ones included), found, converged}.
+ *
+ * sgm_symeig_host: all eigenpairs of a small dense symmetric matrix by cyclic Jacobi, HOST ONLY (no HIP call, usable without a
+ * GPU; m <= 64 takes microseconds there).  H: m x m column-major, both triangles read; theta: m eigenvalues in the order Jacobi
+ * leaves them (NOT sorted); Z: m x m column-major, H Z = Z diag(theta); sweeps (may be NULL): the sweeps taken.  The contract:
+ *     A = H ; Z = I ; sweeps = 0
+ *     repeat at most 64 times:
+ *         every A(p,q), p < q, is exactly 0:  stop
+ *         sweeps += 1
+ *         for p = 0 .. m-2, for q = p+1 .. m-1 (row-major over p < q), where apq = A(p,q) != 0:
+ *             tau = (A(q,q) - A(p,p)) / (2.0*apq) ;  r = sqrt(1.0 + tau*tau)
+ *             t = tau >= 0 ? 1.0/(tau + r) : -1.0/(r - tau)
+ *             c = 1.0/sqrt(1.0 + t*t) ;  s = t*c
+ *             A(p,p) = A(p,p) - t*apq ;  A(q,q) = A(q,q) + t*apq ;  A(p,q) = A(q,p) = 0
+ *             i != p, q:  x = A(i,p) ; y = A(i,q) ;  A(i,p) = A(p,i) = c*x - s*y ;  A(i,q) = A(q,i) = s*x + c*y
+ *             every i:    x = Z(i,p) ; y = Z(i,q) ;  Z(i,p) = c*x - s*y ;  Z(i,q) = s*x + c*y
+ *     theta(i) = A(i,i)
+ *
+ * sgm_basis_rotate: Q[:, 0:kk] <- Q[:, 0:m] Z in place, 1 <= kk <= m <= 64, ldq >= n.  Q: n x m column-major with leading
+ * dimension ldq, on the device (where = SGM_DEVICE; SGM_HOST: copied there and back); Z: m x kk column-major on the HOST.
+ * Entry (i, c) of the result is ((0.0 + Q(i,0) Z(0,c)) + Q(i,1) Z(1,c)) + ... ascending, formed from the row as it was before
+ * the call.  One row per lane, Z in LDS; compulsory traffic 8 n (m + kk) bytes.                                            */
+int sgm_eigsh(sgm_mat A, int32_t k, int32_t ncv, int32_t which /* 0 = smallest algebraic, 1 = largest */, double tol,
+              int32_t max_restarts, const double *q1, double *lambda_out /* k, host */,
+              double *V_out /* n x k column-major, may be NULL */, double *resid_out /* k, host: the TRUE residual norms */,
+              int64_t *info /* restarts, products, found, converged */, int where);
+int sgm_symeig_host(int32_t m, const double *H /* m x m column-major, symmetric */, double *theta, double *Z, int32_t *sweeps);
+int sgm_basis_rotate(int64_t n, int32_t m, int32_t kk, double *Q, int64_t ldq, const double *Z /* m x kk column-major, host */,
+                     int where);
+
 /* ---- row-partitioned multi-GPU (nothing in the reference) ---------------- *
  * One process per GPU.  Rank r owns the contiguous global rows
  * [row_starts[r], row_starts[r+1]) of A and the same slice of every vector.

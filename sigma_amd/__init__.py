@@ -1248,6 +1248,101 @@ def generalized_eigensolve(A, B, n, q1):
     return _ritz(T, Q, False)
 
 
+class EigshResult:
+    """What eigsh returns: lam[k], V[n, k] (or None), residuals[k] (the TRUE |A v - lam v|_2), restarts, products, found,
+    converged.  Entries from `found` on are NaN (lam, residuals) / zero columns (V)."""
+
+    def __init__(self, lam, V, residuals, restarts, products, found, converged):
+        self.lam, self.V, self.residuals = lam, V, residuals
+        self.restarts, self.products, self.found, self.converged = restarts, products, found, converged
+
+    def __repr__(self):
+        return (f"EigshResult(lam={self.lam!r}, residuals={self.residuals!r}, restarts={self.restarts}, products={self.products}, "
+                f"found={self.found}, converged={self.converged})")
+
+
+def eigsh_start_vector(n):
+    """The start vector eigsh uses when none is given: 1 + ((i * 2654435761) mod 1024) / 1024, i = 0 .. n-1 -- exact in
+    float64, the same on every run, not an RNG."""
+    i = np.arange(n, dtype=np.uint64)
+    return 1.0 + ((i * np.uint64(2654435761)) % np.uint64(1024)).astype(np.float64) / 1024.0
+
+
+def eigsh(A, k, which="SA", ncv=None, tol=1e-8, max_restarts=200, q1=None, want_V=True):
+    """sgm_eigsh: the k smallest ("SA") or largest ("LA") algebraic eigenvalues of the symmetric matrix A and their
+    eigenvectors by thick-restart Lanczos on the device (the contract: include/sigma_hip.h).  Convergence is decided by the
+    Lanczos estimate rho <= tol * anorm; `residuals` are the true residual norms.  ncv defaults to min(n - 1, max(2k + 1, 20)).
+    V is a numpy array when q1 is one (or None), a device tensor when q1 is a device tensor."""
+    if hasattr(A, "_build"):
+        A._build()
+    if which not in ("SA", "LA"):
+        raise SigmaError(1, f"eigsh: which must be 'SA' or 'LA', not {which!r}")
+    n = A.nrow
+    if ncv is None:
+        ncv = min(n - 1, max(2 * k + 1, 20))
+    if q1 is None:
+        q1 = eigsh_start_vector(n)
+    pq, w, _k = _arg(q1, np.float64)
+    _need(q1, n, "eigsh q1")
+    kk = max(int(k), 1)
+    lam = np.zeros(kk, np.float64)
+    res = np.zeros(kk, np.float64)
+    info = np.zeros(4, np.int64)
+    V = pv = None
+    if want_V:
+        if w == SGM_DEVICE:
+            import torch
+            V = torch.zeros((kk, n), dtype=torch.float64, device=q1.device)
+            pv = C.c_void_p(V.data_ptr())
+        else:
+            V = np.zeros((kk, n), np.float64)
+            pv = C.c_void_p(V.ctypes.data)
+    _ck(lib().sgm_eigsh(A._h, C.c_int32(int(k)), C.c_int32(int(ncv)), C.c_int32(1 if which == "LA" else 0), C.c_double(float(tol)),
+                        C.c_int32(int(max_restarts)), pq, C.c_void_p(lam.ctypes.data), pv, C.c_void_p(res.ctypes.data),
+                        C.c_void_p(info.ctypes.data), C.c_int(w)))
+    if want_V:
+        V = V.T if w == SGM_DEVICE else V.T.copy()
+    return EigshResult(lam, V, res, int(info[0]), int(info[1]), int(info[2]), bool(info[3]))
+
+
+def symeig_host(H):
+    """sgm_symeig_host: all eigenpairs of a small dense symmetric matrix by cyclic Jacobi, on the host (no GPU needed).
+    Returns (theta[m] in the order Jacobi leaves them, Z[m, m] with H Z = Z diag(theta), sweeps)."""
+    H = np.asarray(H, np.float64)
+    m = H.shape[0]
+    if H.ndim != 2 or H.shape[1] != m:
+        raise SigmaError(2, "symeig_host: H must be a square matrix")
+    Hf = np.asfortranarray(H)
+    theta = np.zeros(m, np.float64)
+    Z = np.zeros((m, m), np.float64, order="F")
+    sweeps = C.c_int32(0)
+    _ck(lib().sgm_symeig_host(C.c_int32(m), C.c_void_p(Hf.ctypes.data), C.c_void_p(theta.ctypes.data), C.c_void_p(Z.ctypes.data),
+                              C.byref(sweeps)))
+    return theta, Z, int(sweeps.value)
+
+
+def basis_rotate(Q, Z):
+    """sgm_basis_rotate: Q[:, 0:kk] <- Q[:, 0:m] Z on the device, Z (m x kk) a numpy array.  Q: a numpy array of shape (n, m) --
+    a rotated copy's first kk columns are returned -- or a device tensor of shape (m, n) holding the columns as contiguous
+    rows, rotated in place (its first kk rows are returned)."""
+    Z = np.asfortranarray(np.asarray(Z, np.float64))
+    m, kk = Z.shape
+    if _is_torch(Q) and Q.is_cuda:
+        if Q.dim() != 2 or Q.shape[0] != m:
+            raise SigmaError(2, f"basis_rotate: a device Q holds its columns as rows: shape ({m}, n) expected")
+        pq, w, _k = _arg(Q, np.float64)
+        n = int(Q.shape[1])
+        _ck(lib().sgm_basis_rotate(C.c_int64(n), C.c_int32(m), C.c_int32(kk), pq, C.c_int64(n), C.c_void_p(Z.ctypes.data), C.c_int(w)))
+        return Q[:kk]
+    Qf = np.array(Q, np.float64, order="F")
+    if Qf.ndim != 2 or Qf.shape[1] != m:
+        raise SigmaError(2, f"basis_rotate: Q must have shape (n, {m})")
+    n = Qf.shape[0]
+    _ck(lib().sgm_basis_rotate(C.c_int64(n), C.c_int32(m), C.c_int32(kk), C.c_void_p(Qf.ctypes.data), C.c_int64(n),
+                               C.c_void_p(Z.ctypes.data), C.c_int(SGM_HOST)))
+    return Qf[:, :kk].copy()
+
+
 def halo_plan_host(n_own, col_begin, node_global):
     """Host-only index work of the row partition (no GPU needed): returns
     (node_local 1-based, halo_cols sorted unique global 1-based)."""

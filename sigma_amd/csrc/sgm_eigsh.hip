@@ -1,0 +1,416 @@
+// sgm_eigsh: the k smallest or largest eigenpairs of a symmetric matrix by thick-restart Lanczos (Wu-Simon), the basis resident in
+// HBM; sgm_basis_rotate, the in-place product Q[:, 0:kk] <- Q[:, 0:m] Z that forms Ritz vectors; sgm_symeig_host, the small dense
+// eigensolver of the projected matrix.  No reference counterpart: the contract is the loop in include/sigma_hip.h (sgm_eigsh),
+// DESIGN.md section 9g points to it, tests/eigsh_restated.py restates it.  Compiled with -ffp-contract=off, no MFMA: every
+// operation is rounded on its own.
+//
+// A Lanczos step is 8 launches with three dependent reductions (h, g, w.w):
+//     w = A q_j                                                  spmv_parts
+//     partial sums of h = Q[:, 0..j]^T w                          k_egs<KB, 0>     basis read once
+//     h                                                           k_eig_reduce     (j + 1 workgroups re-reduce the partial sums)
+//     w -= Q h ; partial sums of g = Q^T w                        k_egs<KB, 1>     basis read once (columns held in registers)
+//     g                                                           k_eig_reduce
+//     w -= Q g ; partial sums of w.w                              k_egs<KB, 2>     basis read once
+//     H(j,j) = h_j + g_j ; beta_j = sqrt(w.w) ; invariant test    k_eig_step       (one workgroup)
+//     q_{j+1} = w * (1.0 / beta_j)                                FEigScale
+// -- three reads of the j + 1 columns and five passes over w, whatever j is.  Nothing in a cycle waits for the host: the step
+// kernel raises a device flag at an invariant subspace (or a NaN) and every later kernel of the cycle returns at once.
+#include "sgm_krylov.hpp"
+#include "sgm_symeig_host.hpp"
+
+#include <numeric>
+
+namespace sgm {
+
+constexpr int kEigMaxNcv = 64;
+constexpr double kEigTiny = 9.094947017729282e-13;        // 2^-40: the invariant-subspace trigger and the smallest tol accepted
+
+// lives in device memory; copied to the host once per cycle (the cycle's one synchronisation)
+struct EigDev {
+    double alpha[kEigMaxNcv];      // H(j,j) of the steps taken
+    double beta[kEigMaxNcv];       // beta_j
+    double scale;                  // max(anorm, |H(i,i)|, beta_i) over the steps of this cycle so far
+    double inv;                    // 1.0 / beta_j of the last step
+    int32_t ncols;                 // columns of the basis that are orthonormal: j + 1 after step j
+    int32_t flag;                  // nonzero: the cycle has ended early (beta_j <= 2^-40 scale, or not a number)
+};
+
+// The Gram-Schmidt passes over the columns 0 .. kk-1 (kk <= KB) of Q, 16-byte accesses, one accumulator per column and thread.
+//   MODE 0:  partial sums of Q^T w                                            -> part_out[c * kMaxGrid + workgroup], c < kk
+//   MODE 1:  w(i) = (..(w(i) - coef_0 q_0(i)) - ..) - coef_{kk-1} q_{kk-1}(i), columns ascending ; then as MODE 0 with the new w
+//   MODE 2:  the same correction ; partial sums of w.w                       -> part_out[workgroup]
+// Thread t of the grid adds the products of elements 2i, 2i+1 for i = t, t + threads, ... (thread 0 then the last element of an
+// odd n): the order of every sum depends on n alone, the grid being dot_grid(n).
+// HOLD: the columns stay in registers between the correction and the dots (kk <= 32); above that they are read again, by the
+// thread that has just read them.
+template <int KB, int MODE>
+__global__ __launch_bounds__(kBlock) void k_egs(int64_t n, int kk, double *__restrict__ w, const double *__restrict__ Q, int64_t ldq,
+                                                const double *__restrict__ coef, double *__restrict__ part_out, const int *flag)
+{
+    constexpr bool HOLD = KB <= 32;
+    __shared__ double red[kBlock / 64];
+    __shared__ double cl[KB];
+    if (*flag) return;
+    if (MODE != 0) {
+        if (threadIdx.x < KB) cl[threadIdx.x] = (int)threadIdx.x < kk ? coef[threadIdx.x] : 0.0;
+        __syncthreads();
+    }
+    constexpr int NACC = MODE == 2 ? 1 : KB;
+    double acc[NACC];
+#pragma unroll
+    for (int c = 0; c < NACC; ++c) acc[c] = 0.0;
+    const int64_t gtid = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    const int64_t n2 = n >> 1;
+    for (int64_t i = gtid; i < n2; i += stride) {
+        double2 wv = ld2<false>(w, i);
+        if constexpr (MODE == 1 && HOLD) {
+            double2 vv[KB];
+#pragma unroll
+            for (int c = 0; c < KB; ++c)
+                if (c < kk) vv[c] = ld2<true>(Q + (size_t)c * ldq, i);
+#pragma unroll
+            for (int c = 0; c < KB; ++c)
+                if (c < kk) { wv.x = wv.x - cl[c] * vv[c].x; wv.y = wv.y - cl[c] * vv[c].y; }
+            st2<false>(w, i, wv);
+#pragma unroll
+            for (int c = 0; c < KB; ++c)
+                if (c < kk) { acc[c] += vv[c].x * wv.x; acc[c] += vv[c].y * wv.y; }
+        } else {
+            if constexpr (MODE != 0) {
+#pragma unroll 8
+                for (int c = 0; c < kk; ++c) {
+                    const double2 v = ld2<MODE == 2>(Q + (size_t)c * ldq, i);
+                    wv.x = wv.x - cl[c] * v.x; wv.y = wv.y - cl[c] * v.y;
+                }
+                st2<false>(w, i, wv);
+            }
+            if constexpr (MODE == 2) { acc[0] += wv.x * wv.x; acc[0] += wv.y * wv.y; }
+            else {
+#pragma unroll
+                for (int c = 0; c < KB; ++c)
+                    if (c < kk) {
+                        const double2 v = ld2<true>(Q + (size_t)c * ldq, i);
+                        acc[c] += v.x * wv.x; acc[c] += v.y * wv.y;
+                    }
+            }
+        }
+    }
+    if ((n & 1) && gtid == 0) {
+        const int64_t i = n - 1;
+        double wv = w[i];
+        if constexpr (MODE != 0) {
+            for (int c = 0; c < kk; ++c) wv = wv - cl[c] * Q[(size_t)c * ldq + i];
+            w[i] = wv;
+        }
+        if constexpr (MODE == 2) acc[0] += wv * wv;
+        else {
+#pragma unroll
+            for (int c = 0; c < KB; ++c)
+                if (c < kk) acc[c] += Q[(size_t)c * ldq + i] * wv;
+        }
+    }
+    if constexpr (MODE == 2) {
+        const double t = block_sum<kBlock>(acc[0], red);
+        if (threadIdx.x == 0) part_out[blockIdx.x] = t;
+    } else {
+#pragma unroll
+        for (int c = 0; c < KB; ++c)
+            if (c < kk) {                        // kk is uniform: every thread takes the same branches
+                const double t = block_sum<kBlock>(acc[c], red);
+                if (threadIdx.x == 0) part_out[(size_t)c * kMaxGrid + blockIdx.x] = t;
+            }
+    }
+}
+
+// workgroup c: slots[c] = the sum of partial array c (load_scalar's order: one array of `count` == 1 is the value itself)
+__global__ __launch_bounds__(kBlock) void k_eig_reduce(const double *parts, int count, double *slots, const int *flag)
+{
+    __shared__ double red[kBlock / 64];
+    if (flag && *flag) return;
+    const double d = load_scalar<kBlock>(ScalarRef{parts + (size_t)blockIdx.x * kMaxGrid, count}, red);
+    if (threadIdx.x == 0) slots[blockIdx.x] = d;
+}
+
+// the end of step j: H(j,j), beta_j, the invariant-subspace test.  first: j is the first step of its cycle (scale starts at anorm)
+__global__ __launch_bounds__(kBlock) void k_eig_step(ScalarRef ww, const double *hs, const double *gs, int j, int first, double anorm,
+                                                     EigDev *S)
+{
+    __shared__ double red[kBlock / 64];
+    if (S->flag) return;
+    const double d = load_scalar<kBlock>(ww, red);
+    if (threadIdx.x != 0) return;
+    const double alpha = hs[j] + gs[j], beta = sqrt(d);
+    double s = first ? anorm : S->scale;
+    if (fabs(alpha) > s) s = fabs(alpha);
+    if (beta > s) s = beta;
+    S->alpha[j] = alpha;
+    S->beta[j] = beta;
+    S->scale = s;
+    S->inv = 1.0 / beta;
+    S->ncols = j + 1;
+    if (!(beta > kEigTiny * s)) S->flag = 1;          // (a beta that is not a number compares false too)
+}
+
+// q_{j+1}(i) = w(i) * (1.0 / beta_j)
+struct FEigScale {
+    static constexpr bool kDot = false;
+    double *dst; const double *src; const EigDev *S; double s = 0.0;
+    __device__ bool prepare(double *) { s = S->inv; return true; }
+    template <bool NT> __device__ void pair(int64_t i)
+    {
+        double2 a = ld2<NT>(src, i); a.x = a.x * s; a.y = a.y * s; st2<NT>(dst, i, a);
+    }
+    __device__ void single(int64_t i) { dst[i] = src[i] * s; }
+    __device__ void finish(double *) {}
+};
+
+// r(i) = y(i) - lambda * v(i) ; partial sums of r.r       (the true residual of one Ritz pair; r itself is not stored)
+struct FEigResid {
+    const double *y, *v; double lambda; double *part; double s = 0.0;
+    __device__ bool prepare(double *) { return true; }
+    __device__ void one(double yv, double vv) { const double r = yv - lambda * vv; s += r * r; }
+    template <bool NT> __device__ void pair(int64_t i)
+    {
+        const double2 a = ld2<NT>(y, i), b = ld2<NT>(v, i);
+        one(a.x, b.x); one(a.y, b.y);
+    }
+    __device__ void single(int64_t i) { one(y[i], v[i]); }
+    __device__ void finish(double *red) { put_partial(s, part, red); }
+};
+
+// Q[:, 0:kk] <- Q[:, 0:m] Z in place: one row per lane, the row's m entries in registers (every column is contiguous, so a wave
+// reads 512 contiguous bytes per column), Z (m x kk, column-major) in LDS, read as broadcasts.  Output c of a row is
+// ((0.0 + q_0 z_0c) + q_1 z_1c) + ..., ascending, and is written over input c only after the whole row has been read: the
+// operation is row-local, so in place is safe.  Compulsory traffic 8 n (m + kk) bytes.
+template <int MB>
+__global__ __launch_bounds__(kBlock) void k_basis_rotate(int64_t n, int m, int kk, double *Q, int64_t ldq, const double *__restrict__ Z)
+{
+    __shared__ double Zl[kEigMaxNcv * kEigMaxNcv];
+    for (int e = threadIdx.x; e < m * kk; e += kBlock) Zl[e] = Z[e];
+    __syncthreads();
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t row = (int64_t)blockIdx.x * kBlock + threadIdx.x; row < n; row += stride) {
+        double q[MB];
+#pragma unroll
+        for (int r = 0; r < MB; ++r) q[r] = r < m ? Q[(size_t)r * ldq + row] : 0.0;
+        for (int c = 0; c < kk; ++c) {
+            const double *zc = Zl + c * m;
+            double s = 0.0;
+#pragma unroll
+            for (int r = 0; r < MB; ++r)
+                if (r < m) s = s + q[r] * zc[r];
+            Q[(size_t)c * ldq + row] = s;
+        }
+    }
+}
+
+static void launch_rotate(int64_t n, int m, int kk, double *Q, int64_t ldq, const double *Zdev)
+{
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n + kBlock - 1) / kBlock, 8192));
+    if (m <= 8) hipLaunchKernelGGL(k_basis_rotate<8>, dim3(grid), dim3(kBlock), 0, g_rt.stream, n, m, kk, Q, ldq, Zdev);
+    else if (m <= 16) hipLaunchKernelGGL(k_basis_rotate<16>, dim3(grid), dim3(kBlock), 0, g_rt.stream, n, m, kk, Q, ldq, Zdev);
+    else if (m <= 32) hipLaunchKernelGGL(k_basis_rotate<32>, dim3(grid), dim3(kBlock), 0, g_rt.stream, n, m, kk, Q, ldq, Zdev);
+    else hipLaunchKernelGGL(k_basis_rotate<64>, dim3(grid), dim3(kBlock), 0, g_rt.stream, n, m, kk, Q, ldq, Zdev);
+}
+
+template <int MODE>
+static void launch_egs(int64_t n, int kk, double *w, const double *Q, int64_t ldq, const double *coef, double *part, const int *flag)
+{
+    const dim3 grid(dot_grid(n)), block(kBlock);
+    if (kk <= 8) hipLaunchKernelGGL((k_egs<8, MODE>), grid, block, 0, g_rt.stream, n, kk, w, Q, ldq, coef, part, flag);
+    else if (kk <= 16) hipLaunchKernelGGL((k_egs<16, MODE>), grid, block, 0, g_rt.stream, n, kk, w, Q, ldq, coef, part, flag);
+    else if (kk <= 32) hipLaunchKernelGGL((k_egs<32, MODE>), grid, block, 0, g_rt.stream, n, kk, w, Q, ldq, coef, part, flag);
+    else hipLaunchKernelGGL((k_egs<64, MODE>), grid, block, 0, g_rt.stream, n, kk, w, Q, ldq, coef, part, flag);
+}
+
+}  // namespace sgm
+
+extern "C" {
+
+int sgm_symeig_host(int32_t m, const double *H, double *theta, double *Z, int32_t *sweeps)
+{
+    if (m < 1 || !H || !theta || !Z) return fail(SGM_ERR_BAD_ARG, "sgm_symeig_host: bad argument");
+    const int32_t sw = symeig_jacobi(m, H, theta, Z);
+    if (sweeps) *sweeps = sw;
+    return SGM_OK;
+}
+
+int sgm_basis_rotate(int64_t n, int32_t m, int32_t kk, double *Q, int64_t ldq, const double *Z, int where)
+{
+    SGM_TRY(require_init());
+    if (n < 1 || m < 1 || m > kEigMaxNcv || kk < 1 || kk > m || !Q || !Z || ldq < n)
+        return fail(SGM_ERR_BAD_ARG, "sgm_basis_rotate: needs n >= 1, 1 <= kk <= m <= 64, ldq >= n");
+    struct Bufs {
+        double *Z = nullptr, *Q = nullptr;
+        ~Bufs() { dfree(Z); dfree(Q); }
+    } b;
+    SGM_TRY(dalloc(&b.Z, (size_t)m * kk));
+    hipStream_t st = g_rt.stream;
+    SGM_HIP(hipMemcpyAsync(b.Z, Z, (size_t)m * kk * 8, hipMemcpyHostToDevice, st));
+    double *Qd = Q;
+    const size_t span = (size_t)ldq * (m - 1) + n;               // the entries between Q(0,0) and Q(n-1,m-1)
+    if (where == SGM_HOST) {
+        SGM_TRY(dalloc(&b.Q, span));
+        SGM_HIP(hipMemcpyAsync(b.Q, Q, span * 8, hipMemcpyHostToDevice, st));
+        Qd = b.Q;
+    }
+    launch_rotate(n, m, kk, Qd, ldq, b.Z);
+    SGM_HIP(hipGetLastError());
+    if (where == SGM_HOST)
+        SGM_HIP(hipMemcpy2DAsync(Q, (size_t)ldq * 8, Qd, (size_t)ldq * 8, (size_t)n * 8, kk, hipMemcpyDeviceToHost, st));
+    SGM_HIP(hipStreamSynchronize(st));        // (Z's device copy is released on return)
+    return SGM_OK;
+}
+
+int sgm_eigsh(sgm_mat A, int32_t k, int32_t ncv, int32_t which, double tol, int32_t max_restarts, const double *q1,
+              double *lambda_out, double *V_out, double *resid_out, int64_t *info, int where)
+{
+    SGM_TRY(require_init());
+    if (!A || !q1 || !lambda_out || !resid_out || !info) return fail(SGM_ERR_BAD_ARG, "sgm_eigsh: null argument");
+    if (A->nrow != A->ncol) return fail(SGM_ERR_DIMS, "sgm_eigsh: square matrices only (%d x %d)", A->nrow, A->ncol);
+    if (A->distributed()) return fail(SGM_ERR_UNSUPPORTED, "sgm_eigsh: row-partitioned and distributed matrices are not supported");
+    const int64_t n = A->nrow;
+    const int m = ncv;
+    if (k < 1 || ncv <= k || ncv > kEigMaxNcv || ncv >= n || !(tol >= kEigTiny) || max_restarts < 0 || (which != 0 && which != 1))
+        return fail(SGM_ERR_BAD_ARG, "sgm_eigsh: needs 1 <= k < ncv <= 64, ncv < n, tol >= 2^-40, max_restarts >= 0, which 0 or 1 "
+                                     "(k %d, ncv %d, n %lld, tol %g, max_restarts %d, which %d)", k, ncv, (long long)n, tol, max_restarts, which);
+    const int64_t ld = (n + 1) & ~(int64_t)1;                     // even leading dimension: 16-byte aligned columns
+    const int gd = dot_grid(n);
+    struct Bufs {
+        double *Q = nullptr, *w = nullptr, *parts = nullptr, *slots = nullptr, *Z = nullptr;
+        EigDev *S = nullptr;
+        ~Bufs() { dfree(Q); dfree(w); dfree(parts); dfree(slots); dfree(Z); dfree(S); }
+    } b;
+    SGM_TRY(dalloc(&b.Q, (size_t)ld * (m + 1) + 2));
+    SGM_TRY(dalloc(&b.w, (size_t)ld + 2));
+    SGM_TRY(dalloc(&b.parts, (size_t)(kEigMaxNcv + 1) * kMaxGrid));
+    SGM_TRY(dalloc(&b.slots, (size_t)3 * kEigMaxNcv));
+    SGM_TRY(dalloc(&b.Z, (size_t)kEigMaxNcv * kEigMaxNcv));
+    SGM_TRY(dalloc(&b.S, 1));
+    hipStream_t st = g_rt.stream;
+    SGM_HIP(hipMemsetAsync(b.Q, 0, ((size_t)ld * (m + 1) + 2) * 8, st));
+    SGM_HIP(hipMemsetAsync(b.w, 0, ((size_t)ld + 2) * 8, st));
+    SGM_HIP(hipMemsetAsync(b.S, 0, sizeof(EigDev), st));
+    double *hs = b.slots, *gs = b.slots + kEigMaxNcv, *rs = b.slots + 2 * kEigMaxNcv;
+    double *P_WW = b.parts + (size_t)kEigMaxNcv * kMaxGrid;
+    auto q = [&](int c) { return b.Q + (size_t)c * ld; };
+    const int *flag = &b.S->flag;
+    const double *cx[1]; double *yy[1];
+    int64_t products = 0;
+    auto product = [&](const double *src, double *dst, const int *fl) -> int {
+        cx[0] = src; yy[0] = dst;
+        return spmv_parts(A, cx, yy, false, nullptr, fl, nullptr);
+    };
+    {   // q_0 = q1 / sqrt(q1.q1)
+        Staged s1;
+        SGM_TRY(stage_in(s1, q1, n, where, true));
+        launch_elem(n, FDot2{s1.dev, s1.dev, nullptr, nullptr, P_WW, nullptr}, nullptr);
+        launch_elem(n, FScaleInv{q(0), s1.dev, ScalarRef{P_WW, gd}}, nullptr);
+        SGM_HIP(hipStreamSynchronize(st));                        // (the staged copy of q1 is released here)
+    }
+
+    std::vector<double> H((size_t)m * m, 0.0), Hb, theta(m), Z((size_t)m * m), Zsel((size_t)m * m);
+    std::vector<int> order(m);
+    EigDev hd;
+    const int keep = std::min(k + (m - k) / 2, m - 1);
+    double anorm = 0.0;
+    int l = 0, nc = 0, found = 0, converged = 0;
+    int64_t restarts = 0;
+    bool nan = false;
+    for (int64_t c = 0;; ++c) {
+        for (int j = l; j < m; ++j) {
+            SGM_TRY(product(q(j), b.w, flag));
+            launch_egs<0>(n, j + 1, b.w, b.Q, ld, nullptr, b.parts, flag);
+            hipLaunchKernelGGL(k_eig_reduce, dim3(j + 1), dim3(kBlock), 0, st, (const double *)b.parts, gd, hs, flag);
+            launch_egs<1>(n, j + 1, b.w, b.Q, ld, hs, b.parts, flag);
+            hipLaunchKernelGGL(k_eig_reduce, dim3(j + 1), dim3(kBlock), 0, st, (const double *)b.parts, gd, gs, flag);
+            launch_egs<2>(n, j + 1, b.w, b.Q, ld, gs, P_WW, flag);
+            hipLaunchKernelGGL(k_eig_step, dim3(1), dim3(kBlock), 0, st, ScalarRef{P_WW, gd}, (const double *)hs, (const double *)gs, j,
+                               j == l ? 1 : 0, anorm, b.S);
+            launch_elem(n, FEigScale{q(j + 1), b.w, b.S}, flag);
+        }
+        SGM_HIP(hipGetLastError());
+        SGM_HIP(hipMemcpyAsync(&hd, b.S, sizeof(EigDev), hipMemcpyDeviceToHost, st));
+        SGM_HIP(hipStreamSynchronize(st));                        // the cycle's one synchronisation
+        nc = hd.ncols;
+        const bool closed = hd.flag != 0;
+        products += nc - l;                                       // (the products of a closed cycle's remaining steps returned at once)
+        for (int j = l; j < nc; ++j) {
+            if (hd.alpha[j] != hd.alpha[j] || hd.beta[j] != hd.beta[j]) nan = true;
+            H[j + (size_t)j * m] = hd.alpha[j];
+            if (j + 1 < nc) H[(j + 1) + (size_t)j * m] = H[j + (size_t)(j + 1) * m] = hd.beta[j];
+        }
+        if (nan) break;
+        Hb.assign((size_t)nc * nc, 0.0);                          // the leading nc x nc block (nc < m only when the space has closed)
+        for (int jc = 0; jc < nc; ++jc)
+            for (int i = 0; i < nc; ++i) Hb[i + (size_t)jc * nc] = H[i + (size_t)jc * m];
+        symeig_jacobi(nc, Hb.data(), theta.data(), Z.data());
+        for (int i = 0; i < nc; ++i) {
+            if (theta[i] != theta[i]) nan = true;
+            if (fabs(theta[i]) > anorm) anorm = fabs(theta[i]);
+        }
+        if (nan) break;
+        std::iota(order.begin(), order.begin() + nc, 0);
+        std::stable_sort(order.begin(), order.begin() + nc,
+                         [&](int a, int c2) { return which == 0 ? theta[a] < theta[c2] : theta[a] > theta[c2]; });
+        if (closed) {                                             // an invariant subspace: every Ritz pair in it is exact, rho = 0
+            found = std::min<int>(k, nc);
+            converged = nc >= k;
+            break;
+        }
+        const double bm = hd.beta[m - 1];
+        bool all = true;
+        for (int i = 0; i < k; ++i)
+            if (!(fabs(bm * Z[(m - 1) + (size_t)order[i] * m]) <= tol * anorm)) all = false;
+        found = k;
+        if (all) { converged = 1; break; }
+        if (c == max_restarts) break;
+        // thick restart: the first `keep` Ritz vectors in that order, then q_m
+        for (int i = 0; i < keep; ++i)
+            for (int r = 0; r < m; ++r) Zsel[r + (size_t)i * m] = Z[r + (size_t)order[i] * m];
+        SGM_HIP(hipMemcpyAsync(b.Z, Zsel.data(), (size_t)m * keep * 8, hipMemcpyHostToDevice, st));
+        launch_rotate(n, m, keep, b.Q, ld, b.Z);
+        launch_elem(n, FCopy{q(keep), q(m)}, nullptr);
+        std::fill(H.begin(), H.end(), 0.0);
+        for (int i = 0; i < keep; ++i) {
+            H[i + (size_t)i * m] = theta[order[i]];
+            H[keep + (size_t)i * m] = H[i + (size_t)keep * m] = bm * Z[(m - 1) + (size_t)order[i] * m];
+        }
+        l = keep;
+        ++restarts;                                               // (Zsel is next written after the next cycle's synchronisation)
+    }
+
+    const double qnan = std::nan("");
+    for (int i = 0; i < k; ++i) lambda_out[i] = resid_out[i] = qnan;
+    if (nan) found = 0, converged = 0;
+    if (found > 0) {
+        // V = Q[:, 0..nc-1] Z[:, wanted] ; resid_i = sqrt(r.r), r = A v_i - lambda_i v_i
+        for (int i = 0; i < found; ++i)
+            for (int r = 0; r < nc; ++r) Zsel[r + (size_t)i * nc] = Z[r + (size_t)order[i] * nc];
+        SGM_HIP(hipMemcpyAsync(b.Z, Zsel.data(), (size_t)nc * found * 8, hipMemcpyHostToDevice, st));
+        SGM_HIP(hipMemsetAsync(&b.S->flag, 0, sizeof(int32_t), st));
+        launch_rotate(n, nc, found, b.Q, ld, b.Z);
+        for (int i = 0; i < found; ++i) {
+            lambda_out[i] = theta[order[i]];
+            ++products;
+            SGM_TRY(product(q(i), b.w, nullptr));
+            launch_elem(n, FEigResid{b.w, q(i), lambda_out[i], b.parts + (size_t)i * kMaxGrid}, nullptr);
+        }
+        hipLaunchKernelGGL(k_eig_reduce, dim3(found), dim3(kBlock), 0, st, (const double *)b.parts, gd, rs, (const int *)nullptr);
+        SGM_HIP(hipGetLastError());
+        SGM_HIP(hipMemcpyAsync(resid_out, rs, (size_t)found * 8, hipMemcpyDeviceToHost, st));
+        if (V_out)
+            SGM_HIP(hipMemcpy2DAsync(V_out, (size_t)n * 8, b.Q, (size_t)ld * 8, (size_t)n * 8, found,
+                                     where == SGM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
+        SGM_HIP(hipStreamSynchronize(st));
+        for (int i = 0; i < found; ++i) resid_out[i] = sqrt(resid_out[i]);
+    }
+    info[0] = restarts;
+    info[1] = products;
+    info[2] = found;
+    info[3] = converged;
+    return SGM_OK;
+}
+
+}  // extern "C"

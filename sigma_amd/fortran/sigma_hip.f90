@@ -27,6 +27,7 @@
 !     sparse_matrix_composites.f90:41-162       set_submatrix, matvec(_t)  !
 !   lanczos(A,T,Q), generalized_lanczos       hip_lanczos,                 !
 !     eigensolver.f90:27-38,95-108              hip_generalized_lanczos    !
+!   (nothing: an extension)                   hip_eigsh: extreme eigenpairs!
 !   add_edge / convert / set_value assembly   hip_csr_from_edges           !
 !   (nothing: "This loop can be parallelized" hip_comm, hip_dist_csr_matrix!
 !     sparse_matrix_composites.f90:1086)        one process per GPU, RCCL  !
@@ -565,6 +566,35 @@ interface
         integer(c_int32_t), value :: nsteps
         real(c_double), intent(in) :: q1(*)
         real(c_double), intent(out) :: T(3, *), Q(*)
+        integer(c_int), value :: where
+        integer(c_int) :: rc
+    end function
+    function sgm_eigsh(A, k, ncv, which, tol, max_restarts, q1, lambda, V, resid, info, where) &
+            & bind(c, name='sgm_eigsh') result(rc)
+        import :: c_ptr, c_int, c_int32_t, c_int64_t, c_double
+        type(c_ptr), value :: A
+        integer(c_int32_t), value :: k, ncv, which, max_restarts
+        real(c_double), value :: tol
+        real(c_double), intent(in) :: q1(*)
+        real(c_double), intent(out) :: lambda(*), V(*), resid(*)
+        integer(c_int64_t), intent(out) :: info(4)
+        integer(c_int), value :: where
+        integer(c_int) :: rc
+    end function
+    function sgm_symeig_host(m, H, theta, Z, sweeps) bind(c, name='sgm_symeig_host') result(rc)
+        import :: c_int, c_int32_t, c_double
+        integer(c_int32_t), value :: m
+        real(c_double), intent(in) :: H(*)
+        real(c_double), intent(out) :: theta(*), Z(*)
+        integer(c_int32_t), intent(out) :: sweeps
+        integer(c_int) :: rc
+    end function
+    function sgm_basis_rotate(n, m, kk, Q, ldq, Z, where) bind(c, name='sgm_basis_rotate') result(rc)
+        import :: c_int, c_int32_t, c_int64_t, c_double
+        integer(c_int64_t), value :: n, ldq
+        integer(c_int32_t), value :: m, kk
+        real(c_double), intent(inout) :: Q(*)
+        real(c_double), intent(in) :: Z(*)
         integer(c_int), value :: where
         integer(c_int) :: rc
     end function
@@ -1958,6 +1988,55 @@ subroutine hip_generalized_lanczos(A, B, solver_for_B, T, Q, q1, pc)
     Q = 0.0_dp
     T(1:3, 1:n) = Tc
     Q(1:A%nrow, 1:n) = Qc
+end subroutine
+
+
+subroutine hip_eigsh(A, k, which, lambda, V, resid, ncv, tol, max_restarts, q1, restarts, products, found, converged)
+    ! no reference counterpart: the k smallest (which = 'SA') or largest ('LA') eigenpairs of the symmetric A by thick-restart
+    ! Lanczos on the device (sgm_eigsh; the contract is in include/sigma_hip.h).  lambda(k); V(nrow, k) (optional); resid(k)
+    ! (optional): the TRUE residual norms.  Defaults: ncv = min(n - 1, max(2k + 1, 20)), tol = 1e-8, max_restarts = 200,
+    ! q1(i) = 1 + mod((i - 1) * 2654435761, 1024) / 1024 (exact, the same on every run)
+    class(hip_matrix), intent(inout) :: A
+    integer, intent(in) :: k
+    character(len=*), intent(in) :: which
+    real(dp), intent(out) :: lambda(:)
+    real(dp), intent(out), optional :: V(:,:), resid(:)
+    integer, intent(in), optional :: ncv, max_restarts
+    real(dp), intent(in), optional :: tol, q1(:)
+    integer, intent(out), optional :: restarts, products, found
+    logical, intent(out), optional :: converged
+    real(dp), allocatable :: q0(:), lc(:), Vc(:,:), rc(:)
+    integer(c_int64_t) :: info(4), i
+    integer :: m, mr, w
+    real(dp) :: t
+    m = min(A%nrow - 1, max(2 * k + 1, 20))
+    mr = 200
+    t = 1.0e-8_dp
+    if (present(ncv)) m = ncv
+    if (present(max_restarts)) mr = max_restarts
+    if (present(tol)) t = tol
+    w = -1
+    if (which == 'SA') w = 0
+    if (which == 'LA') w = 1
+    allocate(q0(A%nrow), lc(max(k, 1)), Vc(A%nrow, max(k, 1)), rc(max(k, 1)))
+    if (present(q1)) then
+        q0 = q1
+    else
+        do i = 1, A%nrow
+            q0(i) = 1.0_dp + real(mod((i - 1) * 2654435761_c_int64_t, 1024_c_int64_t), dp) / 1024.0_dp
+        enddo
+    endif
+    Vc = 0.0_dp
+    call A%upload()
+    call hip_check(sgm_eigsh(A%handle, int(k, c_int32_t), int(m, c_int32_t), int(w, c_int32_t), t, int(mr, c_int32_t), q0, lc, Vc, &
+        & rc, info, SGM_HOST))
+    lambda(1:k) = lc(1:k)
+    if (present(V)) V(1:A%nrow, 1:k) = Vc(:, 1:k)
+    if (present(resid)) resid(1:k) = rc(1:k)
+    if (present(restarts)) restarts = int(info(1))
+    if (present(products)) products = int(info(2))
+    if (present(found)) found = int(info(3))
+    if (present(converged)) converged = info(4) /= 0
 end subroutine
 
 
