@@ -397,10 +397,7 @@ static int coop_arm(sgm_solver s, size_t n /* doubles of exchange vectors in fro
 }
 
 // ---- host: one driver for the four fast-path runners, kernel selection, the order small / cooperative / loop ---------------
-// Run-time values as template arguments: f is called once with a std::integral_constant (sgm_spmv_select.hpp: with_flags).
-template <int V> using Int = std::integral_constant<int, V>;
-template <bool V> using Flag = std::integral_constant<bool, V>;
-template <class F> static bool with_flag(bool v, F &&f) { return v ? f(Flag<true>{}) : f(Flag<false>{}); }
+// (Int<>, Flag<>, with_flag: sgm_internal.hpp)
 // the slice widths with a matrix-in-registers kernel of their own: 3, 5, 7; everything else up to 8 takes the 8-slot one
 template <class F> static bool with_slots(int sw, F &&f) { return sw == 3 ? f(Int<3>{}) : sw == 5 ? f(Int<5>{}) : sw == 7 ? f(Int<7>{}) : f(Int<8>{}); }
 

@@ -9,6 +9,7 @@
 #include <cstring>
 #include <string>
 #include <atomic>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -154,6 +155,12 @@ inline int vec_grid(int64_t n)
     if (g > 2048) g = 2048;            // 256 CUs x 8 resident 256-thread blocks
     return (int)g;
 }
+
+// Run-time values as template arguments of a launch: f is called once with a std::integral_constant
+// (sgm_spmv_select.hpp: with_flags does the same for the product kernels' three flags).
+template <int V> using Int = std::integral_constant<int, V>;
+template <bool V> using Flag = std::integral_constant<bool, V>;
+template <class F> static auto with_flag(bool v, F &&f) { return v ? f(Flag<true>{}) : f(Flag<false>{}); }
 
 // A scalar that lives on the device as `count` partial sums (count == 1: already
 // reduced, e.g. after an all-reduce).  Every consumer block re-reduces the partials in

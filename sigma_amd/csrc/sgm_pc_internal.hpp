@@ -3,7 +3,9 @@
 // preconditioner and the host functions the three call across; sgm_trsv3.hip (the slab pipeline) keeps its own state behind
 // the slab3_* functions of sgm_internal.hpp; sgm_mg.hip and sgm_mg_direct.hip share the mg_direct_* functions at the end.
 // The library is built without relocatable device code: a kernel is launched
-// only from the file that defines it, so everything declared here is a host function.
+// only from the file that defines it, so everything declared here is a host function.  (The device pieces the strip and the
+// slab pipeline have in common -- abort, empty marker, DPP shift, the scatter out of position space -- are inline / static in
+// sgm_trsv_device.hpp, which those two files include: one definition, a copy per file.)
 #pragma once
 #include "sgm_internal.hpp"
 

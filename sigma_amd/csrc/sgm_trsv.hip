@@ -12,9 +12,16 @@
 //       global round trips.
 //   strip pipeline (apply_grid)    grid-like factors (deps r-1, r-w): one launch per sweep, see k_trsv_strip.
 //   row-space sweeps (apply_rows)  factors of a few levels (colour orderings): one launch per level on the vectors
-//       themselves, no position space at all (k_trsv_rows); rows_cg_fused folds PCG's r update and r.z into them.
-// Also here: the elementwise Jacobi apply (scale_by).
+//       themselves, no position space at all; rows_cg_fused folds PCG's r update and r.z into them.  Four kernel families
+//       (one or two rows per lane, plain or fused into PCG) around ONE row recurrence: row_minus_entries and its
+//       two-row form pair_load / pair_minus_entries.  A kernel adds how a row picks up its right-hand side, what a
+//       dependency reads and what is stored.
+// Also here: the elementwise Jacobi apply (scale_by).  The launchers at the end turn run-time values into template arguments
+// through generic lambdas (with_upto2, with_row_slots, with_soa_slots, with_flag); there are no launch macros.  What the
+// strip pipeline shares with the slab pipeline (abort, empty marker, DPP shift, the scatter out of position space) is in
+// sgm_trsv_device.hpp.
 #include "sgm_pc_internal.hpp"
+#include "sgm_trsv_device.hpp"
 
 #include <algorithm>
 #include <type_traits>
@@ -103,6 +110,82 @@ __global__ void k_trsv_wide_soa(const int32_t *__restrict__ wq, const double *__
     xp[p] = z;
 }
 
+// ---- row-space sweeps -----------------------------------------------------------------------------------------------
+// THE row recurrence, written once for the four kernels below: a row's right-hand side minus its entries in stored order,
+//     t = t - val * dep(row of the entry),
+// every product rounded on its own (the build has -ffp-contract=off) -- bit for bit the oracle's sequential sweep.  p = the
+// row's position in the level order, which is where its slots lie in rq / rv (rs_at).  C >= 0: C slots, unrolled, every slot
+// requested before the first is used, nontemporal (read once per sweep: past the caches the gathers live in); C = -1: `rc`
+// slots in a loop (a row's entries fill its first slots).  What dep reads is the caller's business.
+template <int C, class Dep>
+__device__ inline double row_minus_entries(double t, const int32_t *__restrict__ rq, const double *__restrict__ rv, int rc, int32_t p,
+                                           Dep dep)
+{
+    if constexpr (C >= 0) {
+        int32_t q[C > 0 ? C : 1];
+        double v[C > 0 ? C : 1];
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            q[c] = __builtin_nontemporal_load(rq + rs_at(c, p, rc));
+            v[c] = __builtin_nontemporal_load(rv + rs_at(c, p, rc));
+        }
+#pragma unroll
+        for (int c = 0; c < C; ++c)
+            if (q[c] >= 0) t = t - v[c] * dep(q[c]);
+    } else {
+        for (int c = 0; c < rc; ++c) {
+            const int32_t q = rq[rs_at(c, p, rc)];
+            if (q < 0) break;
+            t = t - rv[rs_at(c, p, rc)] * dep(q);
+        }
+    }
+    return t;
+}
+
+// The same for TWO consecutive rows per lane -- positions p, p + 1 (p even) holding rows i, i + 1 -- with 16-byte accesses (8-byte
+// for the row numbers) on every stream: half the memory instructions per byte; the one-row form streams at 4.3-4.8 TB/s where
+// the vector kernels reach 5.6-6.6.  In two steps, because the kernels form the right-hand sides in between: pair_load requests
+// the slots of both rows, pair_minus_entries gathers every operand before either row uses one and runs the two subtraction
+// chains side by side.  Per row the statements of row_minus_entries in their order: same bits.
+// CODED: the dependency rows come from the 4-bit codes (rcode; dl = the factor's rdict in LDS, 15 = no entry) instead of
+// rq: 4 bytes per row instead of 4 * C.
+typedef double f64x2p __attribute__((ext_vector_type(2)));
+typedef int32_t i32x2p __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x2p __attribute__((ext_vector_type(2)));
+template <int C> struct RowPair { i32x2p jj[C]; f64x2p vv[C]; };
+template <int C, bool CODED>
+__device__ inline void pair_load(RowPair<C> &e, const int32_t *__restrict__ rq, const double *__restrict__ rv, int rc,
+                                 const uint32_t *__restrict__ rcode, const int32_t *dl, int32_t p, int32_t i)
+{
+    u32x2p cw;
+    if (CODED) cw = __builtin_nontemporal_load(reinterpret_cast<const u32x2p *>(rcode + p));
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        if (CODED) {
+            const uint32_t na = (cw.x >> (4 * c)) & 15u, nb = (cw.y >> (4 * c)) & 15u;
+            e.jj[c].x = na == 15u ? -1 : i + dl[na];
+            e.jj[c].y = nb == 15u ? -1 : i + 1 + dl[nb];
+        } else
+            e.jj[c] = __builtin_nontemporal_load(reinterpret_cast<const i32x2p *>(rq + rs_at(c, p, rc)));
+        e.vv[c] = __builtin_nontemporal_load(reinterpret_cast<const f64x2p *>(rv + rs_at(c, p, rc)));
+    }
+}
+template <int C, class Dep>
+__device__ inline void pair_minus_entries(const RowPair<C> &e, double &ta, double &tb, Dep dep)
+{
+    double da[C], db[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        da[c] = e.jj[c].x >= 0 ? dep(e.jj[c].x) : 0.0;
+        db[c] = e.jj[c].y >= 0 ? dep(e.jj[c].y) : 0.0;
+    }
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        if (e.jj[c].x >= 0) ta = ta - e.vv[c].x * da[c];
+        if (e.jj[c].y >= 0) tb = tb - e.vv[c].y * db[c];
+    }
+}
+
 // One level in ROW space (factors of a few levels -- what the reference's greedy colouring makes of a matrix: one level per
 // colour): out[i] = src[i] (/ D[i]) - sum over the row's entries, stored order, of val * out[row of the entry];
 // i = the level's rows, through `order` or -- a level that is a run of consecutive rows -- counted from row0.  No gather
@@ -115,9 +198,9 @@ __global__ void k_trsv_wide_soa(const int32_t *__restrict__ wq, const double *__
 // stored; MODE 2: a level of the U sweep, z_i = y_i / D_i - sum val * z(node).  Rows below n0 are L's level 0 when that is
 // the run of rows 0 .. n0-1 (the first colour): their y IS r, so nobody copies it -- whoever wants y(q), q < n0, reads r(q).
 template <int C, int MODE>
-__global__ void k_trsv_rows(const int32_t *__restrict__ rq, const double *__restrict__ rv, uint32_t nstride, int rc,
-                            const int32_t *__restrict__ order, int32_t row0, int32_t begin, int32_t end, const double *r,
-                            double *y, const double *__restrict__ D, double *z, int32_t n0, const int *flag)
+__global__ void k_trsv_rows(const int32_t *__restrict__ rq, const double *__restrict__ rv, int rc, const int32_t *__restrict__ order,
+                            int32_t row0, int32_t begin, int32_t end, const double *r, double *y, const double *__restrict__ D,
+                            double *z, int32_t n0, const int *flag)
 {
     if (flag && *flag) return;
     // tile -> workgroup: the dispatcher deals workgroups b, b + 8, ... to one XCD; they take CONSECUTIVE tiles of 256 positions
@@ -131,25 +214,7 @@ __global__ void k_trsv_rows(const int32_t *__restrict__ rq, const double *__rest
     double t;
     if (MODE == 2) t = (i < n0 ? r[i] : y[i]) / D[i];
     else t = r[i];
-    auto dep = [&](int32_t q) -> double { return MODE == 2 ? z[q] : (q < n0 ? r[q] : y[q]); };
-    if (C >= 0) {
-        int32_t q[C > 0 ? C : 1];
-        double v[C > 0 ? C : 1];
-#pragma unroll
-        for (int c = 0; c < C; ++c) {                       // (read once per sweep: past the caches the gathers live in)
-            q[c] = __builtin_nontemporal_load(rq + rs_at(c, p, rc));
-            v[c] = __builtin_nontemporal_load(rv + rs_at(c, p, rc));
-        }
-#pragma unroll
-        for (int c = 0; c < C; ++c)
-            if (q[c] >= 0) t = t - v[c] * dep(q[c]);
-    } else {
-        for (int c = 0; c < rc; ++c) {
-            const int32_t q = rq[rs_at(c, p, rc)];
-            if (q < 0) break;                              // (a row's entries fill its first slots)
-            t = t - rv[rs_at(c, p, rc)] * dep(q);
-        }
-    }
+    t = row_minus_entries<C>(t, rq, rv, rc, p, [&](int32_t q) -> double { return MODE == 2 ? z[q] : (q < n0 ? r[q] : y[q]); });
     if (MODE == 0) y[i] = t;
     else if (MODE == 1) z[i] = t / D[i];
     else z[i] = t;
@@ -166,7 +231,7 @@ __global__ void k_trsv_rows(const int32_t *__restrict__ rq, const double *__rest
 // Same statements and operand order per row as FCgR<2> + k_trsv_rows<C, 1 / 2>: r and z bit-identical; the dot is summed per
 // block of this grid instead of k_elem's (tree order either way).
 template <int C, int MODE>
-__global__ __launch_bounds__(kBlock) void k_trsv_rows_cg(const int32_t *__restrict__ rq, const double *__restrict__ rv, uint32_t nstride, int rc,
+__global__ __launch_bounds__(kBlock) void k_trsv_rows_cg(const int32_t *__restrict__ rq, const double *__restrict__ rv, int rc,
                                                          const int32_t *__restrict__ order, int32_t row0, int32_t begin, int32_t end, double *r,
                                                          const double *__restrict__ q, ScalarRef res2, ScalarRef dpr, const double *__restrict__ D,
                                                          double *z, double *part, const int *flag, int gen)
@@ -188,26 +253,8 @@ __global__ __launch_bounds__(kBlock) void k_trsv_rows_cg(const int32_t *__restri
         const int32_t i = row0 >= 0 ? row0 + (p - begin) : order[p];
         const double ri = MODE == 1 ? r[i] - alpha * q[i] : r[i];
         if (MODE == 1) r[i] = ri;
-        double t = MODE == 2 ? ri / D[i] : ri;
-        auto dep = [&](int32_t j) -> double { return MODE == 2 ? z[j] : r[j]; };
-        if (C >= 0) {
-            int32_t qq[C > 0 ? C : 1];
-            double v[C > 0 ? C : 1];
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                qq[c] = __builtin_nontemporal_load(rq + rs_at(c, p, rc));
-                v[c] = __builtin_nontemporal_load(rv + rs_at(c, p, rc));
-            }
-#pragma unroll
-            for (int c = 0; c < C; ++c)
-                if (qq[c] >= 0) t = t - v[c] * dep(qq[c]);
-        } else {
-            for (int c = 0; c < rc; ++c) {
-                const int32_t j = rq[rs_at(c, p, rc)];
-                if (j < 0) break;
-                t = t - rv[rs_at(c, p, rc)] * dep(j);
-            }
-        }
+        const double t = row_minus_entries<C>(MODE == 2 ? ri / D[i] : ri, rq, rv, rc, p,
+                                              [&](int32_t j) -> double { return MODE == 2 ? z[j] : r[j]; });
         const double zi = MODE == 1 ? t / D[i] : t;
         z[i] = zi;
         s += ri * zi;
@@ -216,14 +263,8 @@ __global__ __launch_bounds__(kBlock) void k_trsv_rows_cg(const int32_t *__restri
     if (threadIdx.x == 0) part[blockIdx.x] = tot;
 }
 
-// The same with TWO consecutive rows per lane and 16-byte accesses (8-byte for the row numbers) on every stream -- the level
-// is a run of consecutive rows (row0 >= 0) with an even first position and first row, slot stride even; an odd last row
-// goes alone.  Half the memory instructions per byte: the one-row form streams at 4.3-4.8 TB/s where the vector kernels
-// reach 5.6-6.6.  Per row the same statements in the same order: same bits.
-typedef double f64x2p __attribute__((ext_vector_type(2)));
-typedef int32_t i32x2p __attribute__((ext_vector_type(2)));
-// CODED: the dependency rows come from the 4-bit codes (rcode, rdict) instead of rq: 4 bytes per row instead of 4 * C.
-typedef uint32_t u32x2p __attribute__((ext_vector_type(2)));
+// The same with two rows per lane (pair_load / pair_minus_entries) -- the level is a run of consecutive rows (row0 >= 0) whose
+// first position and first row have one parity, slot stride even; an odd first and an odd last row go alone.
 template <int C, int MODE, bool CODED>
 __global__ __launch_bounds__(kBlock) void k_trsv_rows_cg2(const int32_t *__restrict__ rq, const double *__restrict__ rv, int rc,
                                                           const uint32_t *__restrict__ rcode, const int32_t *__restrict__ rdict,
@@ -246,22 +287,17 @@ __global__ __launch_bounds__(kBlock) void k_trsv_rows_cg2(const int32_t *__restr
     double s = 0.0;
     constexpr int TILE = 2 * kBlock;
     auto dep = [&](int32_t j) -> double { return MODE == 2 ? z[j] : r[j]; };
-    // a level that starts at an odd position / row (both odd: the caller checks): its first row alone, the pairs from the next
-    const int32_t peel = begin & 1;
-    if (peel && blockIdx.x == 0 && threadIdx.x == 0 && begin < end) {
-        const int32_t p = begin, i = row0;
+    auto one_row = [&](int32_t p, int32_t i) {               // (k_trsv_rows_cg's row)
         const double ri = MODE == 1 ? r[i] - alpha * q[i] : r[i];
         if (MODE == 1) r[i] = ri;
-        double t = MODE == 2 ? ri / D[i] : ri;
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            const int32_t j = rq[rs_at(c, p, rc)];
-            if (j >= 0) t = t - rv[rs_at(c, p, rc)] * dep(j);
-        }
+        const double t = row_minus_entries<C>(MODE == 2 ? ri / D[i] : ri, rq, rv, rc, p, dep);
         const double zi = MODE == 1 ? t / D[i] : t;
         z[i] = zi;
         s += ri * zi;
-    }
+    };
+    // a level that starts at an odd position / row (both odd: the caller checks): its first row alone, the pairs from the next
+    const int32_t peel = begin & 1;
+    if (peel && blockIdx.x == 0 && threadIdx.x == 0 && begin < end) one_row(begin, row0);
     begin += peel;
     row0 += peel;
     const int32_t tiles = (end - begin + TILE - 1) / TILE, tiles_per_xcd = (tiles + 7) >> 3, wg_per_xcd = gridDim.x >> 3;
@@ -270,70 +306,34 @@ __global__ __launch_bounds__(kBlock) void k_trsv_rows_cg2(const int32_t *__restr
         const int32_t p = begin + tile * TILE + 2 * (int32_t)threadIdx.x;
         if (p >= end) continue;
         const int32_t i = row0 + (p - begin);
-        if (p + 1 < end) {
-            const f64x2p rr = *reinterpret_cast<const f64x2p *>(r + i), dd = *reinterpret_cast<const f64x2p *>(D + i);
-            f64x2p qo;
-            qo.x = 0.0; qo.y = 0.0;
-            if (MODE == 1) qo = *reinterpret_cast<const f64x2p *>(q + i);
-            i32x2p jj[C > 0 ? C : 1];
-            f64x2p vv[C > 0 ? C : 1];
-            u32x2p cw;
-            if (CODED) cw = __builtin_nontemporal_load(reinterpret_cast<const u32x2p *>(rcode + p));
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                if (CODED) {
-                    const uint32_t na = (cw.x >> (4 * c)) & 15u, nb = (cw.y >> (4 * c)) & 15u;
-                    jj[c].x = na == 15u ? -1 : i + dl[na];
-                    jj[c].y = nb == 15u ? -1 : i + 1 + dl[nb];
-                } else
-                    jj[c] = __builtin_nontemporal_load(reinterpret_cast<const i32x2p *>(rq + rs_at(c, p, rc)));
-                vv[c] = __builtin_nontemporal_load(reinterpret_cast<const f64x2p *>(rv + rs_at(c, p, rc)));
-            }
-            const double ra = MODE == 1 ? rr.x - alpha * qo.x : rr.x, rb = MODE == 1 ? rr.y - alpha * qo.y : rr.y;
-            if (MODE == 1) {
-                f64x2p rn; rn.x = ra; rn.y = rb;
-                *reinterpret_cast<f64x2p *>(r + i) = rn;
-            }
-            double ta = MODE == 2 ? ra / dd.x : ra, tb = MODE == 2 ? rb / dd.y : rb;
-            // (the two rows' entries side by side: every slot's operands are requested before either row uses them)
-            double da[C > 0 ? C : 1], db[C > 0 ? C : 1];
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                da[c] = jj[c].x >= 0 ? dep(jj[c].x) : 0.0;
-                db[c] = jj[c].y >= 0 ? dep(jj[c].y) : 0.0;
-            }
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                if (jj[c].x >= 0) ta = ta - vv[c].x * da[c];
-                if (jj[c].y >= 0) tb = tb - vv[c].y * db[c];
-            }
-            f64x2p zn;
-            zn.x = MODE == 1 ? ta / dd.x : ta;
-            zn.y = MODE == 1 ? tb / dd.y : tb;
-            *reinterpret_cast<f64x2p *>(z + i) = zn;
-            s += ra * zn.x;
-            s += rb * zn.y;
-        } else {
-            const double ri = MODE == 1 ? r[i] - alpha * q[i] : r[i];
-            if (MODE == 1) r[i] = ri;
-            double t = MODE == 2 ? ri / D[i] : ri;
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                const int32_t j = rq[rs_at(c, p, rc)];
-                if (j >= 0) t = t - rv[rs_at(c, p, rc)] * dep(j);
-            }
-            const double zi = MODE == 1 ? t / D[i] : t;
-            z[i] = zi;
-            s += ri * zi;
+        if (p + 1 >= end) { one_row(p, i); continue; }
+        const f64x2p rr = *reinterpret_cast<const f64x2p *>(r + i), dd = *reinterpret_cast<const f64x2p *>(D + i);
+        f64x2p qo;
+        qo.x = 0.0; qo.y = 0.0;
+        if (MODE == 1) qo = *reinterpret_cast<const f64x2p *>(q + i);
+        RowPair<C> e;
+        pair_load<C, CODED>(e, rq, rv, rc, rcode, dl, p, i);
+        const double ra = MODE == 1 ? rr.x - alpha * qo.x : rr.x, rb = MODE == 1 ? rr.y - alpha * qo.y : rr.y;
+        if (MODE == 1) {
+            f64x2p rn; rn.x = ra; rn.y = rb;
+            *reinterpret_cast<f64x2p *>(r + i) = rn;
         }
+        double ta = MODE == 2 ? ra / dd.x : ra, tb = MODE == 2 ? rb / dd.y : rb;
+        pair_minus_entries<C>(e, ta, tb, dep);
+        f64x2p zn;
+        zn.x = MODE == 1 ? ta / dd.x : ta;
+        zn.y = MODE == 1 ? tb / dd.y : tb;
+        *reinterpret_cast<f64x2p *>(z + i) = zn;
+        s += ra * zn.x;
+        s += rb * zn.y;
     }
     const double tot = block_sum<kBlock>(s, red);
     if (threadIdx.x == 0) part[blockIdx.x] = tot;
 }
 
-// k_trsv_rows for a level that is a run of consecutive rows: two rows per lane, 16-byte accesses, the dependency rows from
-// the 4-bit codes where the factor has them (CODED) -- the forms k_trsv_rows_cg2 measured (83 / 69 us against 98 / 79 with
-// one row per lane and 4-byte row numbers, n = 1e7).  Per row the statements of k_trsv_rows in their order: same bits.
+// k_trsv_rows for a level that is a run of consecutive rows: two rows per lane, the dependency rows from the 4-bit codes where
+// the factor has them (CODED) -- the forms k_trsv_rows_cg2 measured (83 / 69 us against 98 / 79 with one row per lane and
+// 4-byte row numbers, n = 1e7).
 template <int C, int MODE, bool CODED>
 __global__ __launch_bounds__(kBlock) void k_trsv_rows2(const int32_t *__restrict__ rq, const double *__restrict__ rv, int rc,
                                                        const uint32_t *__restrict__ rcode, const int32_t *__restrict__ rdict, int32_t row0,
@@ -347,21 +347,18 @@ __global__ __launch_bounds__(kBlock) void k_trsv_rows2(const int32_t *__restrict
         __syncthreads();
     }
     auto dep = [&](int32_t j) -> double { return MODE == 2 ? z[j] : (j < n0 ? r[j] : y[j]); };
-    auto rhs = [&](int32_t k) -> double { return MODE == 2 ? (k < n0 ? r[k] : y[k]) : r[k]; };
-    // a level that starts at an odd position / row (both odd, its rows on one side of n0: the caller checks): the first row alone
-    const int32_t peel = begin & 1;
-    if (peel && blockIdx.x == 0 && threadIdx.x == 0 && begin < end) {
-        const int32_t p = begin, i = row0;
-        double t = MODE == 2 ? rhs(i) / D[i] : rhs(i);
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            const int32_t j = rq[rs_at(c, p, rc)];
-            if (j >= 0) t = t - rv[rs_at(c, p, rc)] * dep(j);
-        }
+    auto one_row = [&](int32_t p, int32_t i) {               // (k_trsv_rows' row)
+        double t;
+        if (MODE == 2) t = (i < n0 ? r[i] : y[i]) / D[i];
+        else t = r[i];
+        t = row_minus_entries<C>(t, rq, rv, rc, p, dep);
         if (MODE == 0) y[i] = t;
         else if (MODE == 1) z[i] = t / D[i];
         else z[i] = t;
-    }
+    };
+    // a level that starts at an odd position / row (both odd, its rows on one side of n0: the caller checks): the first row alone
+    const int32_t peel = begin & 1;
+    if (peel && blockIdx.x == 0 && threadIdx.x == 0 && begin < end) one_row(begin, row0);
     begin += peel;
     row0 += peel;
     const int32_t tiles_per_xcd = gridDim.x >> 3;
@@ -369,55 +366,23 @@ __global__ __launch_bounds__(kBlock) void k_trsv_rows2(const int32_t *__restrict
     const int32_t p = begin + tile * 2 * kBlock + 2 * (int32_t)threadIdx.x;
     if (p >= end) return;
     const int32_t i = row0 + (p - begin);
-    if (p + 1 < end) {
-        // (i even: rows i, i + 1 lie on one side of the even n0 or straddle nothing -- n0 odd is the caller's scalar case)
-        const double *src = MODE == 2 ? (i < n0 ? r : y) : r;
-        const f64x2p rr = *reinterpret_cast<const f64x2p *>(src + i);
-        f64x2p dd;
-        dd.x = 1.0; dd.y = 1.0;
-        if (MODE != 0) dd = *reinterpret_cast<const f64x2p *>(D + i);
-        i32x2p jj[C > 0 ? C : 1];
-        f64x2p vv[C > 0 ? C : 1];
-        u32x2p cw;
-        if (CODED) cw = __builtin_nontemporal_load(reinterpret_cast<const u32x2p *>(rcode + p));
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            if (CODED) {
-                const uint32_t na = (cw.x >> (4 * c)) & 15u, nb = (cw.y >> (4 * c)) & 15u;
-                jj[c].x = na == 15u ? -1 : i + dl[na];
-                jj[c].y = nb == 15u ? -1 : i + 1 + dl[nb];
-            } else
-                jj[c] = __builtin_nontemporal_load(reinterpret_cast<const i32x2p *>(rq + rs_at(c, p, rc)));
-            vv[c] = __builtin_nontemporal_load(reinterpret_cast<const f64x2p *>(rv + rs_at(c, p, rc)));
-        }
-        double ta = MODE == 2 ? rr.x / dd.x : rr.x, tb = MODE == 2 ? rr.y / dd.y : rr.y;
-        double da[C > 0 ? C : 1], db[C > 0 ? C : 1];
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            da[c] = jj[c].x >= 0 ? dep(jj[c].x) : 0.0;
-            db[c] = jj[c].y >= 0 ? dep(jj[c].y) : 0.0;
-        }
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            if (jj[c].x >= 0) ta = ta - vv[c].x * da[c];
-            if (jj[c].y >= 0) tb = tb - vv[c].y * db[c];
-        }
-        f64x2p out;
-        out.x = MODE == 1 ? ta / dd.x : ta;
-        out.y = MODE == 1 ? tb / dd.y : tb;
-        *reinterpret_cast<f64x2p *>((MODE == 0 ? y : z) + i) = out;
-    } else {
-        double t = MODE == 2 ? rhs(i) / D[i] : rhs(i);
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            const int32_t j = rq[rs_at(c, p, rc)];
-            if (j >= 0) t = t - rv[rs_at(c, p, rc)] * dep(j);
-        }
-        if (MODE == 0) y[i] = t;
-        else if (MODE == 1) z[i] = t / D[i];
-        else z[i] = t;
-    }
+    if (p + 1 >= end) { one_row(p, i); return; }
+    // (i even: rows i, i + 1 lie on one side of the even n0 or straddle nothing -- n0 odd is the caller's scalar case)
+    const double *src = MODE == 2 ? (i < n0 ? r : y) : r;
+    const f64x2p rr = *reinterpret_cast<const f64x2p *>(src + i);
+    f64x2p dd;
+    dd.x = 1.0; dd.y = 1.0;
+    if (MODE != 0) dd = *reinterpret_cast<const f64x2p *>(D + i);
+    RowPair<C> e;
+    pair_load<C, CODED>(e, rq, rv, rc, rcode, dl, p, i);
+    double ta = MODE == 2 ? rr.x / dd.x : rr.x, tb = MODE == 2 ? rr.y / dd.y : rr.y;
+    pair_minus_entries<C>(e, ta, tb, dep);
+    f64x2p out;
+    out.x = MODE == 1 ? ta / dd.x : ta;
+    out.y = MODE == 1 ? tb / dd.y : tb;
+    *reinterpret_cast<f64x2p *>((MODE == 0 ? y : z) + i) = out;
 }
+
 
 // a run of narrow levels [l0, l1) walked by ONE workgroup.  The row records and right-hand
 // sides are independent of the solve, so they are requested D levels ahead (registers; one
@@ -645,44 +610,26 @@ __global__ __launch_bounds__(TB) void k_trsv_walk_ring(const uint64_t *__restric
 //                own flags (kEdgeEmpty until written): a hand-off costs one memory round trip.
 // Strip ib only ever waits for strip ib-1 -- a workgroup with a smaller index, dispatched no later -- so the launch
 // cannot deadlock; every wait loop is bounded all the same and raises the abort word instead of hanging.
-constexpr int kStripDepth = 32;          // records in flight per lane (16: 0.91 / 1.81 ms per PCG iteration at 1000^2 / 2000^2, 32: 0.85 / 1.66)
+// register slots = records in flight per lane (16: 0.91 / 1.81 ms per PCG iteration at 1000^2 / 2000^2, 32: 0.85 / 1.66).  With
+// all 32 in flight -- 3 memory operations per step, vmcnt counts to 63 -- the compiler drains the queue once per trip of the
+// unrolled loop; the kernel's LA parameter (fewer steps in flight than slots) is there for that experiment.  The launcher
+// instantiates this one depth with LA = DEPTH.
+constexpr int kStripDepth = 32;
 constexpr int kStripChunk = 8;           // steps between LDS hand-offs
 constexpr int kStripRing = 512;          // edge values the LDS rings hold (steps)
-// A wait that gives up marks the sweep (abort_word: cleared by the next sweep's gather, read by the setup self-check) AND the
-// preconditioner's sticky word, which only the host clears: the solvers and sgm_pc_apply read it whenever they synchronise
-// anyway, redo the work with the level walkers and retire the pipeline for this handle -- a result the library itself
-// spoiled never reaches the caller (sgm::pc_abort_word / pc_retire_pipelines).
-__device__ inline void raise_abort(int32_t *abort_word, int32_t *sticky)
-{
-    __hip_atomic_store(abort_word, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (sticky) __hip_atomic_store(sticky, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// "not yet written": a SIGNALLING NaN no subtraction can produce (arithmetic quiets NaNs), so the edge values are their own flags
-constexpr unsigned long long kEdgeEmpty = 0x7FF4A5A5A5A5A5A5ull;
-typedef double f64x2s __attribute__((ext_vector_type(2)));
-__device__ inline double dpp_shift_up(double v, double lane0)
-{
-    // lane l receives lane l-1's v (wave_shr:1 crosses the 16-lane DPP rows on gfx9); lane 0 receives lane0
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    const int slo = __builtin_amdgcn_update_dpp(__double2loint(lane0), lo, 0x138, 0xf, 0xf, false);
-    const int shi = __builtin_amdgcn_update_dpp(__double2hiint(lane0), hi, 0x138, 0xf, 0xf, false);
-    return __hiloint2double(shi, slo);
-}
 // ORDER: 0 = every row subtracts its r-w term first, 1 = every row its r-1 term first, 2 = per-row flag (bit 2)
 template <int DEPTH, int CH, int ORDER, int LA = DEPTH>
 __global__ __launch_bounds__(192) void k_trsv_strip(int32_t NI, int32_t S, const StripRec *__restrict__ rec, double *__restrict__ xp,
-                                                    double *edge, int32_t *progress, const int *flag, int one_xcd, int spin_limit,
-                                                    int32_t *sticky)
+                                                    double *edge, int32_t *progress, const int *flag, int spin_limit, int32_t *sticky)
 {
     __shared__ double in_ring[kStripRing], out_ring[kStripRing], out_scratch[64 + CH];
     __shared__ int in_avail, out_count, out_sent, lds_abort; // steps of left-edge values available / produced by the chain / forwarded
     if (flag && *flag) return;
-    // one_xcd: the grid is 8 x NI and only every eighth workgroup works, so that all strips sit on ONE XCD (round-robin
-    // dispatch) and the neighbour hand-offs are served by one L2; placement only, any mapping is correct
-    if (one_xcd && (blockIdx.x & 7)) return;
+    // (tried: a grid of 8 x NI in which only every eighth workgroup works, so that all strips sit on ONE XCD and one L2 serves
+    // the hand-offs -- 0.83 vs 0.87 ms at 1000^2, 2.06 vs 1.85 at 2000^2: within noise, gone)
     const int lane = threadIdx.x & 63;
     const bool chain = threadIdx.x < 64;
-    const int32_t ib = one_xcd ? blockIdx.x >> 3 : blockIdx.x;
+    const int32_t ib = blockIdx.x;
     int32_t *abort_word = progress + NI;
     if (threadIdx.x == 0) { in_avail = ib == 0 ? S + kStripRing : 0; out_count = 0; out_sent = 0; lds_abort = 0; }
     for (int q = threadIdx.x; q < kStripRing; q += 192) { in_ring[q] = 0.0; out_ring[q] = 0.0; }
@@ -824,7 +771,7 @@ __global__ __launch_bounds__(192) void k_trsv_strip(int32_t NI, int32_t S, const
         }
     }
 }
-// position-space gather / hand-over / scatter of the strip path (padding positions hold 0)
+// position-space gather / hand-over of the strip path (padding positions hold 0; the scatter back is k_pos_scatter, sgm_trsv_device.hpp)
 // (gather and transition also clear the progress words of the sweep that follows)
 __global__ void k_grid_gather(int64_t np, StripRec *__restrict__ rec, const double *__restrict__ src,
                               const int32_t *__restrict__ row, int32_t *__restrict__ progress, int32_t nprog,
@@ -848,37 +795,54 @@ __global__ void k_grid_transition(int64_t np, StripRec *__restrict__ recU, const
     for (int64_t q = p; q < nedge; q += stride) edge[q] = kEdgeEmpty;
     for (; p < np; p += stride) { const int32_t q = mapLU[p]; recU[p].rhs = q >= 0 ? xpL[q] / Dp[p] : 0.0; }   // x = x / D
 }
-__global__ void k_grid_scatter(int64_t np, double *__restrict__ dst, const double *__restrict__ xp,
-                               const int32_t *__restrict__ row, const int *flag)
-{
-    if (flag && *flag) return;
-    int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (; p < np; p += stride) { const int32_t r = row[p]; if (r >= 0) dst[r] = xp[p]; }
-}
 
 // ------------------------------------------------------------------------------ launchers
+// Run-time values as template arguments (Int<>, Flag<>, with_flag: sgm_internal.hpp): f is called once.
+// v = LO .. 2: the MODE of a row-space sweep (the fused CG kernels have no MODE 0), the ORDER of a strip factor
+template <int LO, class F> void with_upto2(int v, F &&f)
+{
+    if constexpr (LO == 0) { if (v == 0) return f(Int<0>{}); }
+    if (v == 1) return f(Int<1>{});
+    f(Int<2>{});
+}
+// most entries of a row of a row-space level -> the C of its kernel: unrolled for 0 .. 4, 6 and 8 slots -- 5 and 7 read one
+// padding slot, which rows_commit (sgm_ildu.hip) sizes the slot arrays for -- and the slot loop (-1) beyond
+template <class F> void with_row_slots(int c, F &&f)
+{
+    switch (c) {
+    case 0: return f(Int<0>{});
+    case 1: return f(Int<1>{});
+    case 2: return f(Int<2>{});
+    case 3: return f(Int<3>{});
+    case 4: return f(Int<4>{});
+    case 5: case 6: return f(Int<6>{});
+    case 7: case 8: return f(Int<8>{});
+    default: return f(Int<-1>{});
+    }
+}
+constexpr bool pair_slots(int C) { return C >= 1 && C <= 4; }          // the two-rows-per-lane kernels exist for these
+// most dependencies of a row of a walkers' level (<= kInline) -> the slots its structure-of-arrays kernel reads
+template <class F> void with_soa_slots(int c, F &&f)
+{
+    if (c <= 2) return f(Int<2>{});
+    if (c == 3) return f(Int<3>{});
+    f(Int<4>{});
+}
+// the structure-of-arrays kernels address a slot with 32-bit byte offsets: 8 bytes * nstride must fit
+bool offsets32(const TriFactor &T) { return T.nstride < (size_t)500000000; }
+
 // one strip-pipelined sweep: G's records hold the right-hand side on entry, xp the solution on exit
 void trsv_grid(const GridTri &G, double *xp, const int *flag, int spin_limit, int32_t *sticky)
 {
-    hipStream_t st = g_rt.stream;
-    constexpr int depth = kStripDepth;
-    constexpr int one_xcd = 0;            // (all strips on one XCD measured 0.83 vs 0.87 ms at 1000^2, 2.06 vs 1.85 at 2000^2: within noise, off)
     // 96 KiB of (unused) dynamic LDS per workgroup: at most ONE strip per CU, so that no two chain waves share a SIMD
     constexpr size_t lds_pad = (size_t)96 * 1024;
-#define STRIP_K(DD, OO, LL)                                                                                                      \
-    do {                                                                                                                         \
-        static bool attr = false;                                                                                                \
-        if (!attr) { (void)hipFuncSetAttribute((const void *)k_trsv_strip<DD, kStripChunk, OO, LL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pad); attr = true; } \
-        hipLaunchKernelGGL((k_trsv_strip<DD, kStripChunk, OO, LL>), dim3(one_xcd ? G.NI * 8 : G.NI), dim3(192), lds_pad, st, G.NI, G.S, \
-                           (const StripRec *)G.rec, xp, G.edge, G.progress, flag, one_xcd, spin_limit, sticky);                  \
-    } while (0)
-    // look-ahead (kStripDepth): 32 register slots with 20 steps in flight (3 memory operations per step, vmcnt counts to 63),
-    // 32 with all 32 in flight (the compiler then drains the queue once per trip of the unrolled loop), or 16
-    if (depth == 20) { if (G.order == 0) STRIP_K(32, 0, 20); else if (G.order == 1) STRIP_K(32, 1, 20); else STRIP_K(32, 2, 20); }
-    else if (depth >= 32) { if (G.order == 0) STRIP_K(32, 0, 32); else if (G.order == 1) STRIP_K(32, 1, 32); else STRIP_K(32, 2, 32); }
-    else { if (G.order == 0) STRIP_K(16, 0, 16); else if (G.order == 1) STRIP_K(16, 1, 16); else STRIP_K(16, 2, 16); }
-#undef STRIP_K
+    with_upto2<0>(G.order, [&](auto O) {
+        const auto kernel = k_trsv_strip<kStripDepth, kStripChunk, decltype(O)::value, kStripDepth>;
+        static bool attr = false;            // (one per ORDER: a static of this instantiation of the lambda)
+        if (!attr) { (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pad); attr = true; }
+        hipLaunchKernelGGL(kernel, dim3(G.NI), dim3(192), lds_pad, g_rt.stream, G.NI, G.S, (const StripRec *)G.rec, xp, G.edge, G.progress,
+                           flag, spin_limit, sticky);
+    });
 }
 
 // one level of a row-space sweep (mode: k_trsv_rows' MODE)
@@ -891,45 +855,20 @@ void launch_rows(const TriFactor &T, const TriFactor::RowLevel &L, int mode, con
     // the level's rows all on one side of it with the pairs aligned to the level's own start
     const bool pairs_ok = L.row0 >= 0 && ((L.row0 ^ b) & 1) == 0 &&
                           (((n0 & 1) == 0 && (L.row0 & 1) == 0) || L.row0 >= n0 || L.row0 + (e - b) <= n0);
-    if (pairs_ok && L.c >= 1 && L.c <= 4) {
-        const bool coded = T.rcode != nullptr;
-        const dim3 g2(8 * (((e - b + 2 * kBlock - 1) / (2 * kBlock) + 7) / 8));
-#define R2_M(CC, MM, CD)                                                                                                        \
-    hipLaunchKernelGGL((k_trsv_rows2<CC, MM, CD>), g2, dim3(kBlock), 0, st, (const int32_t *)T.rq, (const double *)T.rv, T.rc,   \
-                       (const uint32_t *)T.rcode, (const int32_t *)T.rdict, L.row0, b, e, r, y, D, z, n0, flag)
-#define R2_C(CC, MM) do { if (coded) R2_M(CC, MM, true); else R2_M(CC, MM, false); } while (0)
-#define R2(CC) do { if (mode == 0) R2_C(CC, 0); else if (mode == 1) R2_C(CC, 1); else R2_C(CC, 2); } while (0)
-        switch (L.c) {
-        case 1: R2(1); break;
-        case 2: R2(2); break;
-        case 3: R2(3); break;
-        default: R2(4); break;
-        }
-#undef R2
-#undef R2_C
-#undef R2_M
-        return;
-    }
-    const dim3 g(8 * (((e - b + kBlock - 1) / kBlock + 7) / 8));           // (a multiple of 8: see the tile map in the kernel)
-#define ROWS_M(CC, MM)                                                                                                         \
-    hipLaunchKernelGGL((k_trsv_rows<CC, MM>), g, dim3(kBlock), 0, st, (const int32_t *)T.rq, (const double *)T.rv, (uint32_t)T.nstride, \
-                       T.rc, (const int32_t *)T.order, L.row0, b, e, r, y, D, z, n0, flag)
-#define ROWS(CC)                                                                                                               \
-    do {                                                                                                                      \
-        if (mode == 0) ROWS_M(CC, 0); else if (mode == 1) ROWS_M(CC, 1); else ROWS_M(CC, 2);                                    \
-    } while (0)
-    switch (L.c) {
-    case 0: ROWS(0); break;
-    case 1: ROWS(1); break;
-    case 2: ROWS(2); break;
-    case 3: ROWS(3); break;
-    case 4: ROWS(4); break;
-    case 5: case 6: ROWS(6); break;
-    case 7: case 8: ROWS(8); break;
-    default: ROWS(-1); break;
-    }
-#undef ROWS
-#undef ROWS_M
+    const bool pairs = pairs_ok && pair_slots(L.c);
+    const int per_block = pairs ? 2 * kBlock : kBlock;
+    const dim3 g(8 * (((e - b + per_block - 1) / per_block + 7) / 8));      // (a multiple of 8: see the tile map in the kernels)
+    with_row_slots(L.c, [&](auto Cc) { with_upto2<0>(mode, [&](auto Mm) {
+        constexpr int C = decltype(Cc)::value, M = decltype(Mm)::value;
+        if (!pairs)
+            hipLaunchKernelGGL((k_trsv_rows<C, M>), g, dim3(kBlock), 0, st, (const int32_t *)T.rq, (const double *)T.rv, T.rc,
+                               (const int32_t *)T.order, L.row0, b, e, r, y, D, z, n0, flag);
+        else if constexpr (pair_slots(C))
+            with_flag(T.rcode != nullptr, [&](auto CODED) {
+                hipLaunchKernelGGL((k_trsv_rows2<C, M, decltype(CODED)::value>), g, dim3(kBlock), 0, st, (const int32_t *)T.rq, (const double *)T.rv, T.rc,
+                                   (const uint32_t *)T.rcode, (const int32_t *)T.rdict, L.row0, b, e, r, y, D, z, n0, flag);
+            });
+    }); });
 }
 
 constexpr int kRowsCgGrid = 2048;            // blocks per launch (grid-stride): 2 x 2048 partial sums <= kMaxGrid
@@ -937,39 +876,19 @@ void launch_rows_cg(const TriFactor &T, const TriFactor::RowLevel &L, int mode, 
                     const double *D, double *z, double *part, int grid, const int *flag, int gen)
 {
     hipStream_t st = g_rt.stream;
-    if (L.row0 >= 0 && ((L.row0 ^ L.b) & 1) == 0 && L.c >= 1 && L.c <= 4) {           // (both even, or both odd: the kernel peels the first row)
-        const bool coded = T.rcode != nullptr;
-#define ROWS2_M(CC, MM, CD)                                                                                                    \
-    hipLaunchKernelGGL((k_trsv_rows_cg2<CC, MM, CD>), dim3(grid), dim3(kBlock), 0, st, (const int32_t *)T.rq, (const double *)T.rv, T.rc, \
-                       (const uint32_t *)T.rcode, (const int32_t *)T.rdict, L.row0, L.b, L.e, r, q, res2, dpr, D, z, part, flag, gen)
-#define ROWS2(CC) do { if (mode == 1) { if (coded) ROWS2_M(CC, 1, true); else ROWS2_M(CC, 1, false); }                          \
-                       else { if (coded) ROWS2_M(CC, 2, true); else ROWS2_M(CC, 2, false); } } while (0)
-        switch (L.c) {
-        case 1: ROWS2(1); break;
-        case 2: ROWS2(2); break;
-        case 3: ROWS2(3); break;
-        default: ROWS2(4); break;
-        }
-#undef ROWS2
-#undef ROWS2_M
-        return;
-    }
-#define ROWS_M(CC, MM)                                                                                                         \
-    hipLaunchKernelGGL((k_trsv_rows_cg<CC, MM>), dim3(grid), dim3(kBlock), 0, st, (const int32_t *)T.rq, (const double *)T.rv, (uint32_t)T.nstride, \
-                       T.rc, (const int32_t *)T.order, L.row0, L.b, L.e, r, q, res2, dpr, D, z, part, flag, gen)
-#define ROWS(CC) do { if (mode == 1) ROWS_M(CC, 1); else ROWS_M(CC, 2); } while (0)
-    switch (L.c) {
-    case 0: ROWS(0); break;
-    case 1: ROWS(1); break;
-    case 2: ROWS(2); break;
-    case 3: ROWS(3); break;
-    case 4: ROWS(4); break;
-    case 5: case 6: ROWS(6); break;
-    case 7: case 8: ROWS(8); break;
-    default: ROWS(-1); break;
-    }
-#undef ROWS
-#undef ROWS_M
+    const bool pairs = L.row0 >= 0 && ((L.row0 ^ L.b) & 1) == 0 && pair_slots(L.c);      // (both even, or both odd: the kernel peels the first row)
+    with_row_slots(L.c, [&](auto Cc) { with_upto2<1>(mode, [&](auto Mm) {
+        constexpr int C = decltype(Cc)::value, M = decltype(Mm)::value;
+        if (!pairs)
+            hipLaunchKernelGGL((k_trsv_rows_cg<C, M>), dim3(grid), dim3(kBlock), 0, st, (const int32_t *)T.rq, (const double *)T.rv, T.rc,
+                               (const int32_t *)T.order, L.row0, L.b, L.e, r, q, res2, dpr, D, z, part, flag, gen);
+        else if constexpr (pair_slots(C))
+            with_flag(T.rcode != nullptr, [&](auto CODED) {
+                hipLaunchKernelGGL((k_trsv_rows_cg2<C, M, decltype(CODED)::value>), dim3(grid), dim3(kBlock), 0, st, (const int32_t *)T.rq, (const double *)T.rv,
+                                   T.rc, (const uint32_t *)T.rcode, (const int32_t *)T.rdict, L.row0, L.b, L.e, r, q, res2, dpr, D, z, part,
+                                   flag, gen);
+            });
+    }); });
 }
 
 // triangular solve in position space: xp holds the right-hand side on entry, the solution on exit
@@ -979,45 +898,40 @@ void trsv(const TriFactor &T, double *xp, const int *flag)
     hipStream_t st = g_rt.stream;
     for (const auto &L : T.schedule) {
         if (L.narrow) {
-#define WALK(R, DD)                                                                                          \
-    hipLaunchKernelGGL((k_trsv_walk<R, DD>), dim3(1), dim3(kTrsvBlock), 0, st, (const TrsvRec *)T.recs,       \
-                       (const int32_t *)T.pq, (const double *)T.pv, (const int32_t *)T.level_ptr_dev, L.l0, L.l1, \
-                       n, xp, flag)
-#define RING(TT, R, DD, CC, AA)                                                                              \
-    hipLaunchKernelGGL((k_trsv_walk_ring<TT, R, DD, CC, AA>), dim3(1), dim3(TT), 0, st, (const uint64_t *)T.dq, \
-                       (const uint32_t *)T.dq32, (const double *)T.dv, (uint32_t)T.nstride, (const int32_t *)T.level_ptr_dev, L.l0, L.l1, n, xp, \
-                       flag)
-#define RINGC(TT, R, DD, AA)                                                  \
-    do {                                                                      \
-        if (L.c <= 2) RING(TT, R, DD, 2, AA); else if (L.c == 3) RING(TT, R, DD, 3, AA); else RING(TT, R, DD, 4, AA); \
-    } while (0)
-            if (L.ring && T.nstride < (size_t)500000000) {       // (32-bit byte offsets)
+            auto walk = [&](auto R, auto DD) {            // rows per lane, levels requested ahead
+                hipLaunchKernelGGL((k_trsv_walk<decltype(R)::value, decltype(DD)::value>), dim3(1), dim3(kTrsvBlock), 0, st,
+                                   (const TrsvRec *)T.recs, (const int32_t *)T.pq, (const double *)T.pv, (const int32_t *)T.level_ptr_dev,
+                                   L.l0, L.l1, n, xp, flag);
+            };
+            auto ring = [&](auto TB, auto R, auto DD, auto A) { with_soa_slots(L.c, [&](auto C) {      // threads, the two, adjacent rows per lane
+                constexpr int tb = decltype(TB)::value;
+                const auto kernel = k_trsv_walk_ring<tb, decltype(R)::value, decltype(DD)::value, decltype(C)::value, decltype(A)::value>;
+                hipLaunchKernelGGL(kernel, dim3(1), dim3(tb), 0, st, (const uint64_t *)T.dq, (const uint32_t *)T.dq32, (const double *)T.dv,
+                                   (uint32_t)T.nstride, (const int32_t *)T.level_ptr_dev, L.l0, L.l1, n, xp, flag);
+            }); };
+            if (L.ring && offsets32(T)) {
                 // class = widest level of the run: <= 256, 512, 1024, 2048, 4096 rows (two rows per lane pair from 512 on)
                 // (-1: levels of at most 64 rows -- chains: ONE wave, whose level barrier costs nothing)
-                if (L.cls < 0) RINGC(64, 1, 4, 1);
-                else if (L.cls == 0) RINGC(256, 1, 4, 1);
-                else if (L.cls == 1) RINGC(256, 1, 4, 2);
-                else if (L.cls == 2) RINGC(512, 1, 4, 2);
-                else if (L.cls == 3) RINGC(1024, 1, 2, 2);
-                else RINGC(1024, 2, 1, 2);
-            } else if (L.cls <= 2) WALK(1, 2);
-            else if (L.cls == 3) WALK(2, 1);
-            else WALK(4, 1);
-#undef RINGC
-#undef RING
-#undef WALK
+                if (L.cls < 0) ring(Int<64>{}, Int<1>{}, Int<4>{}, Int<1>{});
+                else if (L.cls == 0) ring(Int<256>{}, Int<1>{}, Int<4>{}, Int<1>{});
+                else if (L.cls == 1) ring(Int<256>{}, Int<1>{}, Int<4>{}, Int<2>{});
+                else if (L.cls == 2) ring(Int<512>{}, Int<1>{}, Int<4>{}, Int<2>{});
+                else if (L.cls == 3) ring(Int<1024>{}, Int<1>{}, Int<2>{}, Int<2>{});
+                else ring(Int<1024>{}, Int<2>{}, Int<1>{}, Int<2>{});
+            } else if (L.cls <= 2) walk(Int<1>{}, Int<2>{});
+            else if (L.cls == 3) walk(Int<2>{}, Int<1>{});
+            else walk(Int<4>{}, Int<1>{});
         } else {
             const int32_t b = T.level_ptr[L.l0], e = T.level_ptr[L.l1];
             const dim3 g((e - b + kBlock - 1) / kBlock);
-#define WSOA(CC) hipLaunchKernelGGL((k_trsv_wide_soa<CC>), g, dim3(kBlock), 0, st, (const int32_t *)T.wq, \
-                                    (const double *)T.dv, (uint32_t)T.nstride, b, e, xp, flag)
-            if (L.c <= 2 && T.nstride < (size_t)500000000) WSOA(2);
-            else if (L.c == 3 && T.nstride < (size_t)500000000) WSOA(3);
-            else if (L.c == 4 && T.nstride < (size_t)500000000) WSOA(4);
+            if (L.c <= kInline && offsets32(T))
+                with_soa_slots(L.c, [&](auto C) {
+                    hipLaunchKernelGGL((k_trsv_wide_soa<decltype(C)::value>), g, dim3(kBlock), 0, st, (const int32_t *)T.wq, (const double *)T.dv,
+                                       (uint32_t)T.nstride, b, e, xp, flag);
+                });
             else
                 hipLaunchKernelGGL(k_trsv_wide, g, dim3(kBlock), 0, st, (const TrsvRec *)T.recs, (const int32_t *)T.pq,
                                    (const double *)T.pv, b, e, xp, flag);
-#undef WSOA
         }
     }
 }
@@ -1038,14 +952,14 @@ void apply_grid(const IlduState *S, const double *r, double *z, const int *flag,
                        (const int32_t *)S->gmapLU, (const double *)S->gDp, S->gU.progress, S->gU.NI + 1,
                        reinterpret_cast<unsigned long long *>(S->gU.edge), (int64_t)S->gU.NI * (S->gU.S + kEdgePad), flag);       // x = x / D
     trsv_grid(S->gU, S->gxU, flag, spin_limit, sticky);                                       // (I+U) x = x
-    hipLaunchKernelGGL(k_grid_scatter, dim3(gu), dim3(kBlock), 0, st, S->gU.NP, z, (const double *)S->gxU,
+    hipLaunchKernelGGL(k_pos_scatter, dim3(gu), dim3(kBlock), 0, st, S->gU.NP, z, (const double *)S->gxU,
                        (const int32_t *)S->gU.row, flag);
 }
 
 // the lower sweep's result of the last apply_grid, out of position space (the setup self-check; slab3_lower_result's twin)
 void grid_lower_result(const IlduState *S, double *dst)
 {
-    hipLaunchKernelGGL(k_grid_scatter, dim3(vec_grid(S->gL.NP)), dim3(kBlock), 0, g_rt.stream, S->gL.NP, dst, (const double *)S->gxL,
+    hipLaunchKernelGGL(k_pos_scatter, dim3(vec_grid(S->gL.NP)), dim3(kBlock), 0, g_rt.stream, S->gL.NP, dst, (const double *)S->gxL,
                        (const int32_t *)S->gL.row, (const int *)nullptr);
 }
 

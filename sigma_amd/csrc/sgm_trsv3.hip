@@ -22,7 +22,7 @@
 //     abort word instead of hanging.
 // The path is only trusted with a pattern after it reproduced the row-by-row sweeps bit for bit on a
 // test vector at setup (sgm_pc.hip).
-#include "sgm_internal.hpp"
+#include "sgm_trsv_device.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -34,9 +34,6 @@ namespace {
 constexpr int kPadPos = 32 * 64;           // positions of padding behind the record arrays (the deepest look-ahead)
 constexpr int kEdgeRing = 512;            // lane-63 results a chain wave keeps for the wave to its right
 constexpr int kBig = 1 << 29;
-// "not yet written": a SIGNALLING NaN no subtraction can produce (arithmetic quiets NaNs) -- the forwarded results are their own flags
-constexpr unsigned long long kEmpty = 0x7FF4A5A5A5A5A5A5ull;
-typedef double f64x2s __attribute__((ext_vector_type(2)));
 
 struct SlabTri {
     bool on = false;
@@ -65,14 +62,6 @@ struct Slab3 {
 
 namespace {
 
-__device__ inline double dpp_up(double v, double lane0)
-{
-    // lane l receives lane l-1's v (wave_shr:1 crosses the 16-lane DPP rows on gfx9); lane 0 receives lane0
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    const int slo = __builtin_amdgcn_update_dpp(__double2loint(lane0), lo, 0x138, 0xf, 0xf, false);
-    const int shi = __builtin_amdgcn_update_dpp(__double2hiint(lane0), hi, 0x138, 0xf, 0xf, false);
-    return __hiloint2double(shi, slo);
-}
 __device__ inline int lds_ld(const int *p) { return __hip_atomic_load(p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP); }
 __device__ inline void lds_st(int *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP); }
 
@@ -167,7 +156,7 @@ __global__ __launch_bounds__(TPB) void k_trsv_slab(int32_t NI, int32_t NB, int32
                         __builtin_amdgcn_s_sleep(1);
                         if (++spins > spin_limit || ld_relaxed(lds_abort)) {
                             if (lane == 0) {
-                                { __hip_atomic_store(abort_word, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); if (sticky) __hip_atomic_store(sticky, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+                                raise_abort(abort_word, sticky);
                                 __hip_atomic_store(lds_abort, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                             }
                             return;
@@ -187,7 +176,7 @@ __global__ __launch_bounds__(TPB) void k_trsv_slab(int32_t NI, int32_t NB, int32
                 const int jb = j + 1 - HB, ji = j + HB;
                 const double back_n = jb >= 0 ? cur[(size_t)jb * 64] : prv[(size_t)(DEPTH + jb) * 64];
                 const double inv_n = ji < DEPTH ? cin[(size_t)ji * 64] : pin[(size_t)(ji - DEPTH) * 64];
-                const double left = dpp_up(prev, eE[j % CH]);
+                const double left = dpp_shift_up(prev, eE[j % CH]);
                 const bool first_line = lmod == (j & (HB - 1));         // (t - lane) % HB == 0: t0 is a multiple of HB
                 const double up = first_line ? inv : prev;
                 const uint32_t cc = REG ? 7u : (uint32_t)rc[REG ? 0 : j];
@@ -251,7 +240,7 @@ __global__ __launch_bounds__(TPB) void k_trsv_slab(int32_t NI, int32_t NB, int32
             }
             if (all) return;
             if (any) {
-                // (no wait for the stores to be acknowledged, no flag: a result is kEmpty in memory until it has landed)
+                // (no wait for the stores to be acknowledged, no flag: a result is kEdgeEmpty in memory until it has landed)
                 if (lane == 0 && npass < 128) { htrace[2 * npass] = wall_clock64(); htrace[2 * npass + 1] = made[0]; ++npass; }
 #pragma unroll
                 for (int a = 0; a < kSlabMaxNI; ++a) {
@@ -267,7 +256,7 @@ __global__ __launch_bounds__(TPB) void k_trsv_slab(int32_t NI, int32_t NB, int32
             }
             __builtin_amdgcn_s_sleep(2);
             if (++spins > spin_limit || ld_relaxed(lds_abort)) {
-                if (lane == 0) { __hip_atomic_store(abort_word, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); if (sticky) __hip_atomic_store(sticky, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+                if (lane == 0) raise_abort(abort_word, sticky);
                 return;
             }
         }
@@ -276,7 +265,7 @@ __global__ __launch_bounds__(TPB) void k_trsv_slab(int32_t NI, int32_t NB, int32
     if (b == 0) return;
     long long *htrace = clk + (int64_t)NB * NI * (2 + S / 16) + (int64_t)b * 512 + 256;
     // One memory round trip per pass: load the next kBatch entries of every strip (all loads in flight together) and keep
-    // the leading ones whose 64 values have all landed (kEmpty = not yet; the gather / hand-over kernels reset the arrays).
+    // the leading ones whose 64 values have all landed (kEdgeEmpty = not yet; the gather / hand-over kernels reset the arrays).
     // (Tried: laying consecutive groups onto ONE XCD and reading the upstream results through its L2 with sc0 loads --
     // the producer's sc1 write-through stores do not refresh the L2 line, the reader sees stale data for ~100 us; and a
     // whole sweep's record traffic through one XCD's fabric port halves the chain rate.  Memory (sc1) it is.)
@@ -320,7 +309,7 @@ __global__ __launch_bounds__(TPB) void k_trsv_slab(int32_t NI, int32_t NB, int32
                 bool open = true;
 #pragma unroll
                 for (int u = 0; u < kBatch; ++u) {
-                    const bool landed = __ballot((unsigned long long)__double_as_longlong(v[a][u]) != kEmpty) == ~0ull;
+                    const bool landed = __ballot((unsigned long long)__double_as_longlong(v[a][u]) != kEdgeEmpty) == ~0ull;
                     open = open && landed && base[a] + u < upto[a];
                     if (open) { dst[(size_t)((base[a] + u) & (R - 1)) * 64] = v[a][u]; ++nvalid; }
                 }
@@ -344,7 +333,7 @@ __global__ __launch_bounds__(TPB) void k_trsv_slab(int32_t NI, int32_t NB, int32
             __builtin_amdgcn_s_sleep(1);
             if (++spins > spin_limit || __hip_atomic_load(abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) || ld_relaxed(lds_abort)) {
                 if (lane == 0) {
-                    { __hip_atomic_store(abort_word, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); if (sticky) __hip_atomic_store(sticky, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+                    raise_abort(abort_word, sticky);
                     __hip_atomic_store(lds_abort, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 }
                 return true;
@@ -366,7 +355,8 @@ __global__ __launch_bounds__(TPB) void k_trsv_slab(int32_t NI, int32_t NB, int32
     }
 }
 
-// position-space gather / hand-over / scatter (padding positions hold 0); rhs = second half of a record's second pair
+// position-space gather / hand-over (padding positions hold 0; the scatter back is k_pos_scatter, sgm_trsv_device.hpp);
+// rhs = second half of a record's second pair
 // (both also clear the progress words of the sweep that follows)
 // and mark the sweep's result array "not yet written"
 __global__ void k_slab_gather(int64_t np, f64x2s *__restrict__ rec, const double *__restrict__ src, const int32_t *__restrict__ row,
@@ -376,7 +366,7 @@ __global__ void k_slab_gather(int64_t np, f64x2s *__restrict__ rec, const double
     int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t q = p; q < nprog; q += stride) progress[q] = 0;
-    for (; p < np; p += stride) { const int32_t r = row[p]; rec[2 * p + 1].y = r >= 0 ? src[r] : 0.0; xres[p] = kEmpty; }
+    for (; p < np; p += stride) { const int32_t r = row[p]; rec[2 * p + 1].y = r >= 0 ? src[r] : 0.0; xres[p] = kEdgeEmpty; }
 }
 __global__ void k_slab_transition(int64_t np, f64x2s *__restrict__ recU, const double *__restrict__ xL, const int32_t *__restrict__ mapLU,
                                   const double *__restrict__ Dp, int32_t *__restrict__ progress, int32_t nprog,
@@ -386,14 +376,7 @@ __global__ void k_slab_transition(int64_t np, f64x2s *__restrict__ recU, const d
     int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t q = p; q < nprog; q += stride) progress[q] = 0;
-    for (; p < np; p += stride) { const int32_t q = mapLU[p]; recU[2 * p + 1].y = q >= 0 ? xL[q] / Dp[p] : 0.0; xres[p] = kEmpty; }   // x = x / D
-}
-__global__ void k_slab_scatter(int64_t np, double *__restrict__ dst, const double *__restrict__ xp, const int32_t *__restrict__ row, const int *flag)
-{
-    if (flag && *flag) return;
-    int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (; p < np; p += stride) { const int32_t r = row[p]; if (r >= 0) dst[r] = xp[p]; }
+    for (; p < np; p += stride) { const int32_t q = mapLU[p]; recU[2 * p + 1].y = q >= 0 ? xL[q] / Dp[p] : 0.0; xres[p] = kEdgeEmpty; }   // x = x / D
 }
 
 void free_tri(SlabTri &G)
@@ -764,7 +747,7 @@ void slab3_apply(const Slab3 *S, const double *r, double *z, const int *flag, in
                        (const int32_t *)S->mapLU, (const double *)S->Dp, S->U.progress, S->U.NB * S->U.NI + 1,
                        reinterpret_cast<unsigned long long *>(S->xU), flag);
     trsv_slab(S->U, S->xU, flag, spin_limit, sticky);
-    hipLaunchKernelGGL(k_slab_scatter, dim3(gu), dim3(kBlock), 0, st, S->U.NP, z, (const double *)S->xU, (const int32_t *)S->U.row, flag);
+    hipLaunchKernelGGL(k_pos_scatter, dim3(gu), dim3(kBlock), 0, st, S->U.NP, z, (const double *)S->xU, (const int32_t *)S->U.row, flag);
 }
 
 // abort words of the last sweeps (stream must be idle)
@@ -773,7 +756,7 @@ void slab3_dims(const Slab3 *S, int32_t *w, int32_t *h) { *w = S->L.w; *h = S->L
 // the result of the last L sweep in row order (setup self-check)
 void slab3_lower_result(const Slab3 *S, double *dst)
 {
-    hipLaunchKernelGGL(k_slab_scatter, dim3(vec_grid(S->L.NP)), dim3(kBlock), 0, g_rt.stream, S->L.NP, dst, (const double *)S->xL,
+    hipLaunchKernelGGL(k_pos_scatter, dim3(vec_grid(S->L.NP)), dim3(kBlock), 0, g_rt.stream, S->L.NP, dst, (const double *)S->xL,
                        (const int32_t *)S->L.row, (const int *)nullptr);
 }
 

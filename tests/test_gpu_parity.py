@@ -2135,6 +2135,99 @@ def test_row_space_sweeps_every_slot_count(orc, c):
             pc.set_option("ildu_rows", 1)
 
 
+def _apply_in_every_rows_mode(pc, H, b, want):
+    """pc.solve with ildu_rows 1 (fused levels), 2 (every level launched) and 0 (level walkers), bit for bit against `want`"""
+    for mode in (1, 2, 0):
+        pc.set_option("ildu_rows", mode)
+        try:
+            z = np.zeros(b.size)
+            pc.solve(H, z, b)
+            assert np.array_equal(z, want), mode
+        finally:
+            pc.set_option("ildu_rows", 1)
+
+
+# n0 = rows of the first colour = where L's launched level starts (position and row n0); U's starts at position n - n0 with row 0
+@pytest.mark.parametrize("case,parities", [("90x92", (0, 0)),     # both sweeps: pairs from the first row on
+                                           ("91x91", (1, 0)),     # L: odd position and row, the first row is peeled; U: an odd last row
+                                           ("91x93", (0, 1)),     # U: odd position, row 0 -- one row per lane, counted from row0
+                                           ("5x5x5", (1, 0))])    # six entries: one row per lane, C = 6
+def test_row_space_sweeps_peeled_rows_odd_tails_and_both_parities(orc, case, parities):
+    """The row recurrence the four row-space kernel families share, on two-colour factors whose levels start at every
+    parity: pairs with and without a peeled first row, an odd last row, one row per lane where position and row differ
+    in parity -- the plain sweeps (ildu_rows 1 and 2) and, through a PCG solve, the sweeps fused into CG.  Bit for bit
+    against the oracle's sequential sweeps; the solve at the gates of test_row_space_level_sweeps_of_colour_ordered_factors."""
+    dims = [int(t) for t in case.split("x")]
+    n = int(np.prod(dims))
+    ptr, node, val = P.poisson2d_csr(*dims) if len(dims) == 2 else P.laplace3d_csr(*dims)
+    A = orc.CsrMatrix(n, n, ptr, node, val)
+    H = hip_from_oracle(A)
+    p, ptrs, nc = H.greedy_color_ordering()
+    H.left_permute(p); H.right_permute(p)
+    B = orc.permuted(A, p, p)
+    ref = orc.Ildu(B)
+    pc = sg.ldu()
+    pc.setup(H)
+    assert nc == 2 and list(pc.get("levels", np.int32)) == [2, 2] and list(pc.get("row_levels", np.int32)) == [1, 1, 1]
+    n0 = int(ptrs[1] - ptrs[0])
+    assert (n0 % 2, (n - n0) % 2) == parities, (n0, n)
+    most = max(np.diff(pc.get("Lptr", np.int32)).max(), np.diff(pc.get("Uptr", np.int32)).max())
+    assert most == (4 if len(dims) == 2 else 6)
+    if len(dims) == 2:
+        assert min(n0, n - n0) > 8 * 512            # more tiles than one round of the XCD tile map
+    b = np.random.RandomState(11).standard_normal(n)
+    _apply_in_every_rows_mode(pc, H, b, ref.solve(b))
+    rhs = P.test_vector(n)
+    sol, its = [], []
+    for mode in (0, 1):
+        pc.set_option("ildu_rows", mode)
+        try:
+            s = sg.cg(tolerance=1e-10)
+            s.setup(H)
+            u = np.zeros(n)
+            s.solve(H, u, rhs, pc)
+            sol.append(u); its.append(s.iterations)
+        finally:
+            pc.set_option("ildu_rows", 1)
+    assert abs(its[1] - its[0]) <= 1 and np.abs(sol[1] - sol[0]).max() <= 1e-10 * np.abs(sol[0]).max(), its
+
+
+@pytest.mark.parametrize("g", [1, 7])
+@pytest.mark.parametrize("c", [1, 2, 3, 4])
+def test_row_space_pair_sweeps_coded_and_uncoded(orc, c, g):
+    """test_row_space_sweeps_every_slot_count's three classes with m = 1025 rows each (odd: the level of class 1 starts
+    at an odd position and row -- a peeled first row in MODE 0 and 2 -- and every level has an odd last row) and 1..4 ties
+    per row: the two-rows-per-lane kernels.  Row r of a class is tied to rows (g r + 37 s) mod m of the class before:
+    g = 1 leaves 2c distinct offsets "dependency row - own row" in a factor, which TriFactor::rcode encodes in 4 bits
+    (at most 15); g = 7 leaves hundreds, and the kernels read the dependency rows themselves."""
+    m = 1025
+    n = 3 * m
+    r = np.arange(m)
+    ei, ej = [], []
+    for k in (1, 2):
+        for s in range(c):
+            a = k * m + r
+            b = (k - 1) * m + (g * r + 37 * s) % m
+            ei += [a, b]; ej += [b, a]
+    ei = np.concatenate(ei + [np.arange(n)]) + 1
+    ej = np.concatenate(ej + [np.arange(n)]) + 1
+    rs = np.random.RandomState(10 * c + g)
+    ev = np.concatenate([-rs.uniform(0.1, 1.0, size=ei.size - n), np.full(n, 2.0 * c + 1.0)])
+    A = orc.CsrMatrix.from_edges(n, n, ei.astype(np.int32), ej.astype(np.int32), ev)
+    H = hip_from_oracle(A)
+    ref = orc.Ildu(A)
+    pc = sg.ldu()
+    pc.setup(H)
+    assert list(pc.get("levels", np.int32)) == [3, 3] and list(pc.get("row_levels", np.int32)) == [1, 2, 2]
+    for tri in "LU":
+        tp, tn = pc.get(tri + "ptr", np.int32), pc.get(tri + "node", np.int32)
+        assert set(np.diff(tp)) == {0, c}
+        offsets = np.unique(tn.astype(np.int64) - np.repeat(np.arange(1, n + 1), np.diff(tp)))
+        assert (offsets.size <= 15) if g == 1 else (offsets.size > 15), (tri, offsets.size)
+    b = rs.standard_normal(n)
+    _apply_in_every_rows_mode(pc, H, b, ref.solve(b))
+
+
 def test_lean_footprint_and_on_demand_arrays(orc):
     """Option csr_lean (default on): a matrix served by the 4-bit sliced form keeps only that form + row pointers resident
     (<= 1.15 x what its kernel reads of the matrix); everything that needs the CSR-order arrays -- the other kernels,

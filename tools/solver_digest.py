@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """One JSON line per solve: iteration count, `converged`, SHA-256 of x and of the residual history -- over the cooperative,
-one-workgroup and launch-loop paths of CG and BiCGStab, and one MINRES and one GMRES(30) solve.  Run it on two checkouts
+one-workgroup and launch-loop paths of CG and BiCGStab, one MINRES and one GMRES(30) solve, and the ILDU(0) apply and
+ILDU-preconditioned CG over the triangular sweeps' paths (strips, walkers, slabs, row-space levels).  Run it on two checkouts
 (--tree PATH picks whose sigma_amd is imported), each in a process of its own: a change that moves no rounding leaves the two
 outputs identical.  Public Python API only."""
 import argparse, hashlib, json, os, sys
@@ -83,3 +84,44 @@ for kind in ("cg", "bicgstab"):
     solve("5-point 64x65", kind, 64 * 65, P.poisson2d_csr(64, 65), False, ((small, 0),), tol=1e-300, max_iter=37)
 solve("5-point 64x65", "minres", 64 * 65, P.poisson2d_csr(64, 65))
 solve("5-point 64x65", "gmres", 64 * 65, P.poisson2d_csr(64, 65))
+
+
+def ildu(label, n, csr, colour=False, opts=()):
+    """ILDU(0): SHA-256 of z = M^-1 b from pc.solve, and of x and the history of a CG solve preconditioned with it; the
+    path that served (strips, slabs, row-space levels) rides along"""
+    ptr, node, val = csr
+    A = sg.csr_matrix(n, n, ptr, node, val)
+    if colour:
+        p, _, _ = A.greedy_color_ordering()
+        A.left_permute(p); A.right_permute(p)
+    pc = sg.ldu()
+    for k, v in opts:
+        pc.set_option(k, v)
+    pc.setup(A)
+    b = np.sin(0.01 * np.arange(1, n + 1)) + 0.5
+    z = np.zeros(n)
+    pc.solve(A, z, b)
+    s = sg.cg(1e-9)
+    s.set_history(100000)
+    # (capped: the six-slot band's ILDU(0) is not symmetric -- the explicit 0.0 at +2 fills, nothing at -2 does -- and CG with
+    # it stalls at |r|^2 = 1.04e-17, above the tolerance; a solve has no cap of its own.  The others take 23 .. 181 iterations.)
+    s.set_max_iter(400)
+    s.setup(A)
+    u = np.full(n, 0.25)
+    s.solve(A, u, b, pc, check=False)
+    print(json.dumps({"case": label, "solver": "ildu + cg", "colour": colour, "options": dict(opts), "max_iter": 400,
+                      "path": {k: pc.get(k, np.int32).tolist() for k in ("levels", "strips", "slabs", "row_levels")},
+                      "iterations": int(s.last_iterations), "converged": bool(s.converged),
+                      "z": hashlib.sha256(z.tobytes()).hexdigest(), "x": hashlib.sha256(u.tobytes()).hexdigest(),
+                      "history": hashlib.sha256(np.array(s.history, float).tobytes()).hexdigest()}), flush=True)
+
+
+# the triangular sweeps: strip pipeline and level walkers (natural order), row-space levels fused / unfused / off (colour order)
+for strips in (1, 0):
+    ildu(SHAPES[2][0], SHAPES[2][1], SHAPES[2][2], False, (("ildu_strips", strips),))
+for label, n, csr in (SHAPES[2], ("5-point 91x93", 91 * 93, P.poisson2d_csr(91, 93))):
+    for rows in (1, 2, 0):
+        ildu(label, n, csr, True, (("ildu_rows", rows),))
+for colour in (False, True):
+    ildu(SHAPES[4][0], SHAPES[4][1], SHAPES[4][2], colour)
+ildu(SHAPES[5][0], SHAPES[5][1], SHAPES[5][2])
