@@ -662,6 +662,80 @@ int sgm_symeig_host(int32_t m, const double *H /* m x m column-major, symmetric 
 int sgm_basis_rotate(int64_t n, int32_t m, int32_t kk, double *Q, int64_t ldq, const double *Z /* m x kk column-major, host */,
                      int where);
 
+/* ---- smallest eigenpairs with a preconditioner: generalized Davidson ------------------- *
+ * sgm_davidson <- NO reference counterpart: the k smallest algebraic eigenvalues of a SYMMETRIC matrix and their
+ * eigenvectors by the generalized Davidson method with thick restart.  The search space is expanded by M^-1 r, r the residual
+ * of the first Ritz pair that has not converged and M a preconditioner the caller has set up on A (Jacobi, ILDU(0), the
+ * multigrid V-cycle -- whatever sgm_pc_setup accepts for A; NULL: M = I): with a V-cycle the number of steps does not grow with
+ * the grid, where sgm_eigsh "SA" needs a number of products that does.  Symmetry of A and definiteness of M are NOT checked.
+ * The search space V and its image W = A V (ncv columns each, and two work vectors: 8 (2 ncv + 2) n bytes) never leave HBM.
+ * Single-GPU CSR, ELLPACK and composite matrices; row-partitioned and distributed ones are SGM_ERR_UNSUPPORTED, a non-square
+ * one SGM_ERR_DIMS; k < 1, ncv <= k, ncv > 64, ncv >= n, tol < 2^-40 (or not a number), max_steps < 0, a null pointer, a
+ * preconditioner of any kind whose last setup was not on a matrix of A's size (none at all included): SGM_ERR_BAD_ARG, before
+ * anything is launched -- its apply would read and write vectors of another length; a multigrid preconditioner whose last
+ * setup on such a matrix failed: the error of its apply.  The call after a refusal works.
+ *
+ * The contract (this comment is its one statement: DESIGN.md 9h points here, tests/davidson_restated.py restates it).  Every
+ * operation is rounded on its own (no FMA); `A u` is the library's product; `a.b` is sgm_eigsh's dot product (above: its order
+ * is a function of n alone); `M^-1 u` is the preconditioner's apply, a copy when pc is NULL; V and W hold ncv columns with an
+ * even leading dimension; H is the projected matrix, on the host; keep = min(k + (ncv - k)/2, ncv - 1) with integer division.
+ *     t = 1.0/sqrt(q1.q1) ;  V_0(:) = q1(:) * t ;  W_0 = A V_0 ;  H(0,0) = V_0.W_0
+ *     m = 1 ;  locked = 0 ;  anorm = 0 ;  steps = restarts = 0
+ *     loop:
+ *       a NaN in H[0:m, 0:m]:  leave with found = 0, converged = 0
+ *       (theta, Z) = symeig(H[0:m, 0:m])    (sgm_symeig_host) ;  a NaN in theta:  leave with found = 0, converged = 0
+ *       anorm = max(anorm, max_i |theta_i|) ;  order the Ritz values ascending, ties by index
+ *       while locked < min(k, m):
+ *           c = order[locked] ;  z = Z[:, c]
+ *           u(i) = ((0.0 + V(i,0) z_0) + V(i,1) z_1) + ...  ascending over the m columns ;  y(i) the same over W
+ *           r(i) = y(i) - theta_c * u(i) ;  rn = sqrt(r.r)
+ *           rn <= tol * anorm:  locked += 1      otherwise: leave the while (r is the residual the step expands with)
+ *       locked == k:          for j = 0 .. (locked at the start of this pass of the loop) - 1, ascending:
+ *                                 c = order[j] ;  u, y, r, rn as above ;  not (rn <= tol * anorm):  locked = j, stop looking
+ *       locked == k:          leave with found = k, converged = 1
+ *       locked == m:          leave with found = m, converged = 0       (every Ritz pair of a space smaller than k has
+ *                                                                         converged: nothing to expand from)
+ *       steps == max_steps:   leave with found = min(k, m), converged = 0
+ *       m == ncv:   V[:, 0..keep-1] = V[:, 0..m-1] * Z[:, first keep in that order]   (sgm_basis_rotate's sums) ;  W the same
+ *                   H = 0 ;  H(i,i) = theta of the kept i ;  theta = those, Z = I, the order 0, 1, .. ;  m = keep ;
+ *                   restarts += 1                                                     (r stays as computed)
+ *       t = M^-1 r ;  tau = sqrt(t.t)
+ *       h_i = V_i.t, i = 0..m-1 ;  t(:) = (..(t(:) - h_0 V_0(:)) - ..) - h_{m-1} V_{m-1}(:)   (columns ascending, every subtraction rounded)
+ *       g_i = V_i.t, i = 0..m-1 ;  t(:) = (..(t(:) - g_0 V_0(:)) - ..) - g_{m-1} V_{m-1}(:)   (second classical Gram-Schmidt pass)
+ *       beta = sqrt(t.t)
+ *       a NaN in tau or beta:      leave with found = 0, converged = 0
+ *       not (beta > 2^-40 * tau):  leave with found = min(k, locked), converged = 0   (the preconditioned residual lies in the space)
+ *       s = 1.0/beta ;  V_m(:) = t(:) * s ;  W_m = A V_m ;  H(i,m) = H(m,i) = V_i.W_m for i = 0..m ;  m += 1 ;  steps += 1
+ *     end:
+ *       Vout = V[:, 0..m-1] * Z[:, first `found` in that order]                      (sgm_basis_rotate)
+ *       lambda_i = theta_i
+ *       resid_i = sqrt(r.r), r(:) = y(:) - lambda_i * v_i(:), y = A v_i               (on the device, one product per pair)
+ * rn is the residual of the Ritz pair AS THE TWO BASES GIVE IT (W z - theta V z; W = A V holds up to the roundings of the
+ * rotations); it is the number compared with tol * anorm (anorm: the largest |Ritz value| seen, a lower bound of |A|_2), and it
+ * is not what is returned: resid_out is always the TRUE residual norm |A v - lambda v|_2 of the returned pair, from a product of
+ * its own, as in sgm_eigsh.  Locked pairs are NOT frozen: no column is deflated, every Rayleigh-Ritz step derives them again
+ * from the grown space (which can only lower a Ritz value), and `locked` is a COUNT: while the space grows they are not tested
+ * again.  A Ritz value that comes down between two locked ones -- the second copy of a double eigenvalue that the space met late
+ * -- moves the later ones on by one and takes a locked place without having been tested; that is why the pairs locked in
+ * earlier passes are looked at once more before the call says "converged" (k - 1 passes over the bases at most, at the end),
+ * and the first one that fails becomes the pair to expand with.  resid_out reports what came of them all.
+ * 2^-40 is the contract constant of sgm_eigsh.  A NaN anywhere (the matrix, the preconditioner, q1 -- a zero q1 gives 0 * inf --)
+ * ends with converged = 0 and found = 0, never "converged"; the call still returns SGM_OK.
+ * Host-device traffic: two synchronisations per step.  H's new column (with tau, beta and the flag of the test on them) comes
+ * to the host for the Jacobi sweeps, and z goes back; then r.r comes to the host, once more for every pair that is locked in
+ * that step.  Within a step nothing else waits for the host: a failed test raises a device flag and the step's remaining
+ * kernels return at once.  Against a V-cycle of tens of launches these two are not what a step costs.
+ * One pass per step reads both bases (u, y, r and the partial sums of r.r in one kernel; compulsory traffic 8 n (2m + 1) bytes);
+ * the orthogonalisation reads V three times, the new column of H reads it once more; a restart reads and writes V and W once.
+ * q1: n entries (host or device per `where`).  lambda_out, resid_out: k entries on the HOST; entries from `found` on are NaN.
+ * V_out (may be NULL): n x k column-major, host or device per `where`; only the first `found` columns are written.
+ * info (host, 6 entries): {steps, products with A (W_0, one per step, the residual ones), applies of the preconditioner (0
+ * without one), restarts, found, converged}.                                                                              */
+int sgm_davidson(sgm_mat A, sgm_pc pc_or_null, int32_t k, int32_t ncv, double tol, int32_t max_steps, const double *q1,
+                 double *lambda_out /* k, host */, double *V_out /* n x k column-major, may be NULL */,
+                 double *resid_out /* k, host: the TRUE residual norms */,
+                 int64_t *info /* steps, products, applies, restarts, found, converged */, int where);
+
 /* ---- row-partitioned multi-GPU (nothing in the reference) ---------------- *
  * One process per GPU.  Rank r owns the contiguous global rows
  * [row_starts[r], row_starts[r+1]) of A and the same slice of every vector.

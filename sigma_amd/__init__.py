@@ -1305,6 +1305,60 @@ def eigsh(A, k, which="SA", ncv=None, tol=1e-8, max_restarts=200, q1=None, want_
     return EigshResult(lam, V, res, int(info[0]), int(info[1]), int(info[2]), bool(info[3]))
 
 
+class DavidsonResult(EigshResult):
+    """What davidson returns: EigshResult's fields with `steps` (expansions of the search space) and `applies` (of the
+    preconditioner; 0 without one) added."""
+
+    def __init__(self, lam, V, residuals, steps, products, applies, restarts, found, converged):
+        super().__init__(lam, V, residuals, restarts, products, found, converged)
+        self.steps, self.applies = steps, applies
+
+    def __repr__(self):
+        return (f"DavidsonResult(lam={self.lam!r}, residuals={self.residuals!r}, steps={self.steps}, products={self.products}, "
+                f"applies={self.applies}, restarts={self.restarts}, found={self.found}, converged={self.converged})")
+
+
+def davidson(A, k, pc=None, ncv=None, tol=1e-8, max_steps=1000, q1=None, want_V=True):
+    """sgm_davidson: the k smallest algebraic eigenvalues of the symmetric matrix A and their eigenvectors by the generalized
+    Davidson method with thick restart on the device (the contract: include/sigma_hip.h).  pc: a preconditioner that has been
+    set up on A (jacobi(), ldu(), multigrid(...)), or None; with a V-cycle the step count does not grow with the grid.  A pair
+    counts as converged when the residual the two bases give is <= tol * anorm; `residuals` are the true residual norms.
+    ncv defaults to min(n - 1, max(2k + 1, 20)).  V is a numpy array when q1 is one (or None), a device tensor when q1 is a
+    device tensor."""
+    if hasattr(A, "_build"):
+        A._build()
+    if pc is not None and not isinstance(pc, _Preconditioner):
+        raise SigmaError(1, f"davidson: pc must be a preconditioner (jacobi(), ldu(), multigrid(..)) or None, not {type(pc).__name__}")
+    if pc is not None and not pc._h:
+        raise SigmaError(1, "davidson: the preconditioner has not been set up (pc.setup(A))")
+    n = A.nrow
+    if ncv is None:
+        ncv = min(n - 1, max(2 * int(k) + 1, 20))
+    if q1 is None:
+        q1 = eigsh_start_vector(n)
+    pq, w, _k = _arg(q1, np.float64)
+    _need(q1, n, "davidson q1")
+    kk = max(int(k), 1)
+    lam = np.zeros(kk, np.float64)
+    res = np.zeros(kk, np.float64)
+    info = np.zeros(6, np.int64)
+    V = pv = None
+    if want_V:
+        if w == SGM_DEVICE:
+            import torch
+            V = torch.zeros((kk, n), dtype=torch.float64, device=q1.device)
+            pv = C.c_void_p(V.data_ptr())
+        else:
+            V = np.zeros((kk, n), np.float64)
+            pv = C.c_void_p(V.ctypes.data)
+    _ck(lib().sgm_davidson(A._h, pc._h if pc is not None else None, C.c_int32(int(k)), C.c_int32(int(ncv)), C.c_double(float(tol)),
+                           C.c_int32(int(max_steps)), pq, C.c_void_p(lam.ctypes.data), pv, C.c_void_p(res.ctypes.data),
+                           C.c_void_p(info.ctypes.data), C.c_int(w)))
+    if want_V:
+        V = V.T if w == SGM_DEVICE else V.T.copy()
+    return DavidsonResult(lam, V, res, int(info[0]), int(info[1]), int(info[2]), int(info[3]), int(info[4]), bool(info[5]))
+
+
 def symeig_host(H):
     """sgm_symeig_host: all eigenpairs of a small dense symmetric matrix by cyclic Jacobi, on the host (no GPU needed).
     Returns (theta[m] in the order Jacobi leaves them, Z[m, m] with H Z = Z diag(theta), sweeps)."""

@@ -84,6 +84,17 @@ bool pc_apply_is_short(sgm_pc pc)
     return true;
 }
 const double *pc_idiag(sgm_pc pc, size_t part) { return pc->parts[part].idiag; }
+// pc_apply_parts(pc, A, ..) finds what it reads and stays inside vectors of A's length: the preconditioner's last setup was
+// on a matrix of A's size (pc->n: 0 before any setup) and, for Jacobi and ILDU(0), of A's parts.  (A multigrid preconditioner
+// whose last setup FAILED on a matrix of that size passes here and is refused by mg_apply.)
+bool pc_serves(sgm_pc pc, sgm_mat A)
+{
+    if (!pc || !A) return false;
+    if (pc->n != A->nrow) return false;
+    if (pc->kind == SGM_PC_MG) return true;
+    if (pc->kind == SGM_PC_JACOBI) return !pc->parts.empty() && pc->parts.size() >= A->parts.size() && pc->parts[0].idiag;
+    return !pc->ild.empty() && pc->ild.size() == A->parts.size();
+}
 
 // ILDU(0) of the colour-ordered matrix (option ildu_reorder): the permuted matrix the factors belong to (null: none / natural
 // order).  A solver that finds one runs in the permuted order: x and b through pc_permute_vec once each way, the products on

@@ -28,6 +28,8 @@
 !   lanczos(A,T,Q), generalized_lanczos       hip_lanczos,                 !
 !     eigensolver.f90:27-38,95-108              hip_generalized_lanczos    !
 !   (nothing: an extension)                   hip_eigsh: extreme eigenpairs!
+!   (nothing: an extension)                   hip_davidson: the smallest   !
+!                                               ones with a preconditioner !
 !   add_edge / convert / set_value assembly   hip_csr_from_edges           !
 !   (nothing: "This loop can be parallelized" hip_comm, hip_dist_csr_matrix!
 !     sparse_matrix_composites.f90:1086)        one process per GPU, RCCL  !
@@ -578,6 +580,18 @@ interface
         real(c_double), intent(in) :: q1(*)
         real(c_double), intent(out) :: lambda(*), V(*), resid(*)
         integer(c_int64_t), intent(out) :: info(4)
+        integer(c_int), value :: where
+        integer(c_int) :: rc
+    end function
+    function sgm_davidson(A, pc, k, ncv, tol, max_steps, q1, lambda, V, resid, info, where) &
+            & bind(c, name='sgm_davidson') result(rc)
+        import :: c_ptr, c_int, c_int32_t, c_int64_t, c_double
+        type(c_ptr), value :: A, pc
+        integer(c_int32_t), value :: k, ncv, max_steps
+        real(c_double), value :: tol
+        real(c_double), intent(in) :: q1(*)
+        real(c_double), intent(out) :: lambda(*), V(*), resid(*)
+        integer(c_int64_t), intent(out) :: info(6)
         integer(c_int), value :: where
         integer(c_int) :: rc
     end function
@@ -2037,6 +2051,57 @@ subroutine hip_eigsh(A, k, which, lambda, V, resid, ncv, tol, max_restarts, q1, 
     if (present(products)) products = int(info(2))
     if (present(found)) found = int(info(3))
     if (present(converged)) converged = info(4) /= 0
+end subroutine
+
+
+subroutine hip_davidson(A, k, lambda, pc, V, resid, ncv, tol, max_steps, q1, steps, products, applies, restarts, found, converged)
+    ! no reference counterpart: the k smallest eigenpairs of the symmetric A by the generalized Davidson method with thick
+    ! restart on the device (sgm_davidson; the contract is in include/sigma_hip.h).  pc (optional): a preconditioner that has
+    ! been set up on A (hip_jacobi(), hip_ldu(), hip_multigrid(..)).  lambda(k); V(nrow, k) (optional); resid(k) (optional):
+    ! the TRUE residual norms.  Defaults: ncv = min(n - 1, max(2k + 1, 20)), tol = 1e-8, max_steps = 1000, q1 = hip_eigsh's
+    class(hip_matrix), intent(inout) :: A
+    integer, intent(in) :: k
+    real(dp), intent(out) :: lambda(:)
+    type(hip_linear_solver), intent(in), optional :: pc
+    real(dp), intent(out), optional :: V(:,:), resid(:)
+    integer, intent(in), optional :: ncv, max_steps
+    real(dp), intent(in), optional :: tol, q1(:)
+    integer, intent(out), optional :: steps, products, applies, restarts, found
+    logical, intent(out), optional :: converged
+    real(dp), allocatable :: q0(:), lc(:), Vc(:,:), rc(:)
+    integer(c_int64_t) :: info(6), i
+    integer :: m, ms
+    real(dp) :: t
+    type(c_ptr) :: hp
+    m = min(A%nrow - 1, max(2 * k + 1, 20))
+    ms = 1000
+    t = 1.0e-8_dp
+    if (present(ncv)) m = ncv
+    if (present(max_steps)) ms = max_steps
+    if (present(tol)) t = tol
+    hp = c_null_ptr
+    if (present(pc)) hp = pc%handle
+    allocate(q0(A%nrow), lc(max(k, 1)), Vc(A%nrow, max(k, 1)), rc(max(k, 1)))
+    if (present(q1)) then
+        q0 = q1
+    else
+        do i = 1, A%nrow
+            q0(i) = 1.0_dp + real(mod((i - 1) * 2654435761_c_int64_t, 1024_c_int64_t), dp) / 1024.0_dp
+        enddo
+    endif
+    Vc = 0.0_dp
+    call A%upload()
+    call hip_check(sgm_davidson(A%handle, hp, int(k, c_int32_t), int(m, c_int32_t), t, int(ms, c_int32_t), q0, lc, Vc, rc, info, &
+        & SGM_HOST))
+    lambda(1:k) = lc(1:k)
+    if (present(V)) V(1:A%nrow, 1:k) = Vc(:, 1:k)
+    if (present(resid)) resid(1:k) = rc(1:k)
+    if (present(steps)) steps = int(info(1))
+    if (present(products)) products = int(info(2))
+    if (present(applies)) applies = int(info(3))
+    if (present(restarts)) restarts = int(info(4))
+    if (present(found)) found = int(info(5))
+    if (present(converged)) converged = info(6) /= 0
 end subroutine
 
 
