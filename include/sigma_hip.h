@@ -566,7 +566,12 @@ int sgm_solver_destroy(sgm_solver s);
  * column-major Lanczos vectors.  q1 is the start vector (the reference draws it from a
  * time-seeded RNG); it is normalised inside.  A may be row-partitioned: an in-process partition takes and
  * returns global vectors, a rank of a matrix distributed over processes its owned slice of q1 and Q (n_local x nsteps);
- * the dots are all-reduced, T is the same on every rank.                                    */
+ * the dots are all-reduced, T is the same on every rank.
+ * Every sum of both routines is taken in the device's defined order, a function of n alone (sgm_eigsh below, "Dot products"),
+ * with one exception: on a leaf matrix (one CSR or ELLPACK part) the alpha of sgm_lanczos comes out of the product kernel's
+ * epilogue, in that kernel's own order (what sgm_mat_matvec_dots reports).  On composites and in-process partitions alpha is a
+ * sum in the device's order like every other; over ranks each sum is reduced to a slot and all-reduced.
+ * (tests/lanczos_restated.py restates both loops; tests/test_gpu_lanczos.py holds T and Q to it bit for bit.) */
 int sgm_lanczos(sgm_mat A, int32_t nsteps, const double *q1, double *T_host, double *Q_out, int where);
 
 /* sgm_generalized_lanczos <- generalized_lanczos(A, B, T, Q)  src/eigensolver.f90:95-155: Lanczos for
