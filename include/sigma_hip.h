@@ -741,6 +741,80 @@ int sgm_davidson(sgm_mat A, sgm_pc pc_or_null, int32_t k, int32_t ncv, double to
                  double *resid_out /* k, host: the TRUE residual norms */,
                  int64_t *info /* steps, products, applies, restarts, found, converged */, int where);
 
+/* ---- smallest eigenpairs of A x = lambda B x: Davidson in the B-inner product ---------- *
+ * sgm_davidson_gen <- NO reference counterpart (the reference states this problem for generalized_lanczos only, with a solve
+ * with B in every step): the k smallest eigenvalues of A x = lambda B x, A SYMMETRIC, B SYMMETRIC POSITIVE DEFINITE, and their
+ * B-orthonormal eigenvectors (V^T B V = I) by sgm_davidson's method carried out in the B-inner product.  No system with B is
+ * solved: a step costs one product with B, one with A and one apply of the preconditioner, which the caller has set up on A
+ * exactly as for sgm_davidson (NULL: M = I).  Symmetry of A and B is NOT checked; definiteness of B is checked where the loop
+ * meets it (d below).  The search space V and its images W = A V and U = B V (ncv columns each, and three work vectors:
+ * 8 (3 ncv + 3) n bytes) never leave HBM.
+ * A: single-GPU CSR, ELLPACK or composite; B: the same; they may differ in format.  Before anything is launched: a
+ * row-partitioned or distributed A or B is SGM_ERR_UNSUPPORTED; a non-square A or B, or sizes that differ, SGM_ERR_DIMS; a null
+ * pointer (B included) and sgm_davidson's argument limits (k < 1, ncv <= k, ncv > 64, ncv >= n, tol < 2^-40 or not a number,
+ * max_steps < 0, a preconditioner that does not serve A) SGM_ERR_BAD_ARG.  The call after a refusal works.
+ *
+ * The contract (this comment is its one statement: DESIGN.md 9i points here, tests/davidson_gen_restated.py restates it).
+ * Every operation is rounded on its own (no FMA); `A u` and `B u` are the library's products; `a.b` is sgm_eigsh's dot product
+ * (its order is a function of n alone); rotations use sgm_basis_rotate's sums; V, W and U hold ncv columns with an even leading
+ * dimension; H is the projected matrix, on the host; keep = min(k + (ncv - k)/2, ncv - 1) as in sgm_davidson.
+ *     p = B q1 ;  d = q1.p ;  not (d > 0):  leave with found = 0, converged = 0            (a NaN compares false)
+ *     t = 1.0/sqrt(d) ;  V_0(:) = q1(:) * t ;  U_0(:) = p(:) * t ;  W_0 = A V_0 ;  H(0,0) = V_0.W_0
+ *     m = 1 ;  locked = 0 ;  anorm = 0 ;  steps = restarts = 0
+ *     loop:
+ *       the NaN tests of H and theta, (theta, Z) = symeig(H[0:m, 0:m]), anorm, the ascending order:  as sgm_davidson
+ *       the residual of the pair c = order[j], z = Z[:, c]:
+ *           y(i) = ((0.0 + W(i,0) z_0) + W(i,1) z_1) + ...  ascending over the m columns ;  p(i) the same over U
+ *           r(i) = y(i) - theta_c * p(i) ;  rn = sqrt(r.r) ;  pn = sqrt(p.p)
+ *           it meets the test when  rn <= (tol * anorm) * pn
+ *       the while that locks, the second look at the pairs locked earlier, the three ways out (locked == k, locked == m,
+ *       steps == max_steps):  as sgm_davidson, with that test
+ *       m == ncv:   the thick restart of sgm_davidson with Zk in place of Z[:, first keep in that order], Zk = those columns,
+ *                   each z divided by sqrt(((0.0 + z_0 z_0) + z_1 z_1) + ...) (ascending, on the host) ;  the rotation by Zk
+ *                   applied to V, to W and to U
+ *       t = M^-1 r ;  tau = sqrt(t.t)
+ *       h_i = U_i.t, i = 0..m-1 ;  t(:) = (..(t(:) - h_0 V_0(:)) - ..) - h_{m-1} V_{m-1}(:)   (columns ascending, every subtraction rounded)
+ *       g_i = U_i.t, i = 0..m-1 ;  t(:) = (..(t(:) - g_0 V_0(:)) - ..) - g_{m-1} V_{m-1}(:) ;  nu = sqrt(t.t)
+ *       a NaN in tau or nu:       leave with found = 0, converged = 0
+ *       not (nu > 2^-40 * tau):   leave with found = min(k, locked), converged = 0
+ *       p = B t ;  d = t.p ;  not (d > 0):  leave with found = 0, converged = 0     (B is not positive definite, or a NaN)
+ *       s = 1.0/sqrt(d) ;  V_m(:) = t(:) * s ;  U_m(:) = p(:) * s ;  W_m = A V_m
+ *       H(i,m) = H(m,i) = V_i.W_m for i = 0..m ;  m += 1 ;  steps += 1
+ *     end:
+ *       Vout = V[:, 0..m-1] * Zf, Zf = Z[:, first `found` in that order], every column divided the same way   (sgm_basis_rotate)
+ *       lambda_i = theta_i
+ *       resid_i = sqrt(r.r), r(:) = y(:) - lambda_i * p(:), y = A v_i, p = B v_i      (on the device, two products per pair)
+ * Correction and dots use different bases: the Gram-Schmidt correction subtracts columns of V, the dots are taken against
+ * columns of U = B V.  h_i = U_i.t is the B-inner product of V_i and t, so this IS classical Gram-Schmidt, twice, in the
+ * B-inner product -- with no product with B inside it.  The one product with B of a step is p = B t, which gives the B-norm
+ * of the new direction and the new column of U at once.
+ * The test is relative to |B v|_2: p = U z is B times the Ritz vector as the bases give it, and a pair meets the test when
+ * |W z - theta U z|_2 <= tol * anorm * |U z|_2.  With B = I that is sgm_davidson's test up to the rounding of |v|_2 (there
+ * the vector has norm 1 by construction and is not measured).  The test does not change when A is scaled (r and anorm scale
+ * alike) or when B is (theta U z and U z do): it needs no norm of B.
+ * The columns of Z are normalised before a rotation, which sgm_davidson does not do: cyclic Jacobi leaves |z|_2 = 1 only to
+ * a few tens of eps (8e-15 at m = 20), a rotation by such a z multiplies the B-norm of a kept column by |z|_2, and the factors
+ * of the restarts accumulate in the columns that stay -- after 18 restarts V^T B V had 1 + 1e-13 on its diagonal.  With the
+ * division a restart costs the kept columns one rounding of their norm, and V^T B V = I holds to a few eps whatever the number
+ * of restarts.  The Ritz vector of the residual test is not normalised: rn / pn does not depend on |z|_2.
+ * U is a rotated copy, not a recomputation: U = B V holds only up to the roundings of the scalings and the rotations, as
+ * W = A V does in sgm_davidson, and rn is the residual AS THE BASES GIVE IT.  resid_out is always the TRUE residual norm
+ * |A v - lambda B v|_2 of the returned pair, from two products of its own.
+ * Locked pairs are not frozen; 2^-40, the NaN rule (found = 0, converged = 0, the call returns SGM_OK) and the two
+ * synchronisations per step are sgm_davidson's: H's new column comes to the host with tau, nu and the flag, then r.r and p.p in
+ * one copy.  A failed test (nu, or d) raises a device flag and the step's remaining kernels return at once.
+ * Counts: a step that ends at one of its tests counts none of that step's products.  Products with A: W_0, one per step, one
+ * per returned pair.  Products with B: the first (p = B q1, counted even when its d fails), one per step, one per returned pair.
+ * One pass per step reads W and U (y, p, r and the partial sums of r.r and p.p in one kernel; compulsory traffic 8 n (2m + 1)
+ * bytes, as sgm_davidson's); the orthogonalisation reads U twice and V twice, H's new column reads V once more; a restart reads
+ * and writes V, W and U once.
+ * q1, lambda_out, resid_out, V_out: as sgm_davidson.  info (host, 7 entries): {steps, products with A, products with B, applies
+ * of the preconditioner (0 without one), restarts, found, converged}.                                                     */
+int sgm_davidson_gen(sgm_mat A, sgm_mat B, sgm_pc pc_or_null, int32_t k, int32_t ncv, double tol, int32_t max_steps,
+                     const double *q1, double *lambda_out /* k, host */, double *V_out /* n x k column-major, may be NULL */,
+                     double *resid_out /* k, host: the TRUE |A v - lambda B v|_2 */,
+                     int64_t *info /* steps, products with A, products with B, applies, restarts, found, converged */, int where);
+
 /* ---- row-partitioned multi-GPU (nothing in the reference) ---------------- *
  * One process per GPU.  Rank r owns the contiguous global rows
  * [row_starts[r], row_starts[r+1]) of A and the same slice of every vector.

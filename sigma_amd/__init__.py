@@ -1307,24 +1307,29 @@ def eigsh(A, k, which="SA", ncv=None, tol=1e-8, max_restarts=200, q1=None, want_
 
 class DavidsonResult(EigshResult):
     """What davidson returns: EigshResult's fields with `steps` (expansions of the search space) and `applies` (of the
-    preconditioner; 0 without one) added."""
+    preconditioner; 0 without one) added, and `products_B` (products with the mass matrix; 0 without one)."""
 
-    def __init__(self, lam, V, residuals, steps, products, applies, restarts, found, converged):
+    def __init__(self, lam, V, residuals, steps, products, applies, restarts, found, converged, products_B=0):
         super().__init__(lam, V, residuals, restarts, products, found, converged)
-        self.steps, self.applies = steps, applies
+        self.steps, self.applies, self.products_B = steps, applies, products_B
 
     def __repr__(self):
         return (f"DavidsonResult(lam={self.lam!r}, residuals={self.residuals!r}, steps={self.steps}, products={self.products}, "
-                f"applies={self.applies}, restarts={self.restarts}, found={self.found}, converged={self.converged})")
+                f"applies={self.applies}, restarts={self.restarts}, found={self.found}, converged={self.converged}, "
+                f"products_B={self.products_B})")
 
 
-def davidson(A, k, pc=None, ncv=None, tol=1e-8, max_steps=1000, q1=None, want_V=True):
+def davidson(A, k, pc=None, ncv=None, tol=1e-8, max_steps=1000, q1=None, want_V=True, B=None):
     """sgm_davidson: the k smallest algebraic eigenvalues of the symmetric matrix A and their eigenvectors by the generalized
     Davidson method with thick restart on the device (the contract: include/sigma_hip.h).  pc: a preconditioner that has been
     set up on A (jacobi(), ldu(), multigrid(...)), or None; with a V-cycle the step count does not grow with the grid.  A pair
     counts as converged when the residual the two bases give is <= tol * anorm; `residuals` are the true residual norms.
     ncv defaults to min(n - 1, max(2k + 1, 20)).  V is a numpy array when q1 is one (or None), a device tensor when q1 is a
-    device tensor."""
+    device tensor.
+    B (a symmetric positive definite matrix of A's size, any single-GPU format): sgm_davidson_gen -- the k smallest eigenvalues
+    of A x = lam B x with V^T B V = I, one product with B per step and no solve with it; a pair counts as converged when
+    |W z - theta U z| <= tol * anorm * |U z| (U = B V), `residuals` are the true |A v - lam B v|_2, `products_B` counts the
+    products with B.  pc stays a preconditioner set up on A."""
     if hasattr(A, "_build"):
         A._build()
     if pc is not None and not isinstance(pc, _Preconditioner):
@@ -1332,6 +1337,13 @@ def davidson(A, k, pc=None, ncv=None, tol=1e-8, max_steps=1000, q1=None, want_V=
     if pc is not None and not pc._h:
         raise SigmaError(1, "davidson: the preconditioner has not been set up (pc.setup(A))")
     n = A.nrow
+    if B is not None:
+        if not isinstance(B, _Matrix):
+            raise SigmaError(1, f"davidson: B must be a matrix (csr_matrix, ellpack_matrix, sparse_matrix) or None, not {type(B).__name__}")
+        if hasattr(B, "_build"):
+            B._build()
+        if (B.nrow, B.ncol) != (n, n):
+            raise SigmaError(2, f"davidson: B is {B.nrow} x {B.ncol}, A has {n} rows")
     if ncv is None:
         ncv = min(n - 1, max(2 * int(k) + 1, 20))
     if q1 is None:
@@ -1341,7 +1353,7 @@ def davidson(A, k, pc=None, ncv=None, tol=1e-8, max_steps=1000, q1=None, want_V=
     kk = max(int(k), 1)
     lam = np.zeros(kk, np.float64)
     res = np.zeros(kk, np.float64)
-    info = np.zeros(6, np.int64)
+    info = np.zeros(7, np.int64)
     V = pv = None
     if want_V:
         if w == SGM_DEVICE:
@@ -1351,12 +1363,19 @@ def davidson(A, k, pc=None, ncv=None, tol=1e-8, max_steps=1000, q1=None, want_V=
         else:
             V = np.zeros((kk, n), np.float64)
             pv = C.c_void_p(V.ctypes.data)
-    _ck(lib().sgm_davidson(A._h, pc._h if pc is not None else None, C.c_int32(int(k)), C.c_int32(int(ncv)), C.c_double(float(tol)),
-                           C.c_int32(int(max_steps)), pq, C.c_void_p(lam.ctypes.data), pv, C.c_void_p(res.ctypes.data),
-                           C.c_void_p(info.ctypes.data), C.c_int(w)))
+    tail = (C.c_int32(int(k)), C.c_int32(int(ncv)), C.c_double(float(tol)), C.c_int32(int(max_steps)), pq, C.c_void_p(lam.ctypes.data),
+            pv, C.c_void_p(res.ctypes.data), C.c_void_p(info.ctypes.data), C.c_int(w))
+    hp = pc._h if pc is not None else None
+    if B is None:
+        _ck(lib().sgm_davidson(A._h, hp, *tail))
+        steps, products, applies, restarts, found, converged = (int(x) for x in info[:6])
+        products_B = 0
+    else:
+        _ck(lib().sgm_davidson_gen(A._h, B._h, hp, *tail))
+        steps, products, products_B, applies, restarts, found, converged = (int(x) for x in info)
     if want_V:
         V = V.T if w == SGM_DEVICE else V.T.copy()
-    return DavidsonResult(lam, V, res, int(info[0]), int(info[1]), int(info[2]), int(info[3]), int(info[4]), bool(info[5]))
+    return DavidsonResult(lam, V, res, steps, products, applies, restarts, found, bool(converged), products_B)
 
 
 def symeig_host(H):

@@ -30,32 +30,6 @@ namespace sgm {
 
 bool pc_serves(sgm_pc pc, sgm_mat A);       // sgm_pc.hip
 
-// lives in device memory; read by the host with H's new column
-struct DavDev {
-    double tau;                    // sqrt(t.t) before the orthogonalisation
-    double beta;                   // sqrt(t.t) after it
-    double inv;                    // 1.0 / beta (at the start: 1.0 / sqrt(q1.q1))
-    int32_t flag;                  // nonzero: not (beta > 2^-40 tau) -- the step ends here
-    int32_t pad;
-};
-
-// inv = 1.0 / sqrt(ww) ; with_tau: tau = sqrt(tt), beta = sqrt(ww) and the test of the step
-__global__ __launch_bounds__(kBlock) void k_dav_norm(ScalarRef ww, ScalarRef tt, int with_tau, DavDev *S)
-{
-    __shared__ double red[kBlock / 64];
-    if (S->flag) return;
-    const double d = load_scalar<kBlock>(ww, red);
-    const double e = with_tau ? load_scalar<kBlock>(tt, red) : 0.0;
-    if (threadIdx.x != 0) return;
-    const double beta = sqrt(d);
-    S->beta = beta;
-    S->inv = 1.0 / beta;
-    if (!with_tau) return;
-    const double tau = sqrt(e);
-    S->tau = tau;
-    if (!(beta > kEigTiny * tau)) S->flag = 1;          // (a beta or tau that is not a number compares false too)
-}
-
 // One pass over the rows of V and W (n x m each, leading dimension ld, even): for row i
 //     u = ((0.0 + V(i,0) z_0) + V(i,1) z_1) + ... ; y the same over W ; r(i) = y - theta * u
 // r is stored, u and y are not; the partial sums of r.r are left in the order of k_egs (thread t of the grid dot_grid(n) takes

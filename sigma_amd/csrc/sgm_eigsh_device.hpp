@@ -1,7 +1,8 @@
 // Shared by the eigensolver translation units (sgm_eigsh.hip: thick-restart Lanczos, sgm_basis_rotate; sgm_davidson.hip:
-// generalized Davidson): the passes over a basis resident in HBM -- classical Gram-Schmidt with its dots, the re-reduction of
-// their partial sums, the in-place rotation by a small matrix -- and the two functors both loops end with.  One definition, a
-// copy per file (the library is built without relocatable device code): the non-template kernel is `static`.
+// generalized Davidson; sgm_davidson_gen.hip: the same for A x = lambda B x): the passes over a basis resident in HBM --
+// classical Gram-Schmidt with its dots, the re-reduction of their partial sums, the in-place rotation by a small matrix --
+// the two functors the loops end with, and what a Davidson step leaves for the host.  One definition, a copy per file (the
+// library is built without relocatable device code): the non-template kernels are `static`.
 #pragma once
 #include "sgm_krylov.hpp"
 
@@ -133,6 +134,33 @@ struct FEigResid {
     __device__ void single(int64_t i) { one(y[i], v[i]); }
     __device__ void finish(double *red) { put_partial(s, part, red); }
 };
+
+// What a Davidson step leaves for the host (sgm_davidson.hip, sgm_davidson_gen.hip); lives in device memory and is read
+// with H's new column
+struct DavDev {
+    double tau;                    // sqrt(t.t) before the orthogonalisation
+    double beta;                   // sqrt(t.t) after it
+    double inv;                    // 1.0 / beta (at the start: 1.0 / sqrt(q1.q1))
+    int32_t flag;                  // nonzero: not (beta > 2^-40 tau) -- the step ends here
+    int32_t pad;
+};
+
+// inv = 1.0 / sqrt(ww) ; with_tau: tau = sqrt(tt), beta = sqrt(ww) and the test of the step
+static __global__ __launch_bounds__(kBlock) void k_dav_norm(ScalarRef ww, ScalarRef tt, int with_tau, DavDev *S)
+{
+    __shared__ double red[kBlock / 64];
+    if (S->flag) return;
+    const double d = load_scalar<kBlock>(ww, red);
+    const double e = with_tau ? load_scalar<kBlock>(tt, red) : 0.0;
+    if (threadIdx.x != 0) return;
+    const double beta = sqrt(d);
+    S->beta = beta;
+    S->inv = 1.0 / beta;
+    if (!with_tau) return;
+    const double tau = sqrt(e);
+    S->tau = tau;
+    if (!(beta > kEigTiny * tau)) S->flag = 1;          // (a beta or tau that is not a number compares false too)
+}
 
 // Q[:, 0:kk] <- Q[:, 0:m] Z in place: one row per lane, the row's m entries in registers (every column is contiguous, so a wave
 // reads 512 contiguous bytes per column), Z (m x kk, column-major) in LDS, read as broadcasts.  Output c of a row is

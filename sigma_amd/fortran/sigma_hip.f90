@@ -30,6 +30,8 @@
 !   (nothing: an extension)                   hip_eigsh: extreme eigenpairs!
 !   (nothing: an extension)                   hip_davidson: the smallest   !
 !                                               ones with a preconditioner !
+!   (nothing: an extension)                   hip_davidson_gen: the same   !
+!                                               for A x = lambda B x       !
 !   add_edge / convert / set_value assembly   hip_csr_from_edges           !
 !   (nothing: "This loop can be parallelized" hip_comm, hip_dist_csr_matrix!
 !     sparse_matrix_composites.f90:1086)        one process per GPU, RCCL  !
@@ -592,6 +594,18 @@ interface
         real(c_double), intent(in) :: q1(*)
         real(c_double), intent(out) :: lambda(*), V(*), resid(*)
         integer(c_int64_t), intent(out) :: info(6)
+        integer(c_int), value :: where
+        integer(c_int) :: rc
+    end function
+    function sgm_davidson_gen(A, B, pc, k, ncv, tol, max_steps, q1, lambda, V, resid, info, where) &
+            & bind(c, name='sgm_davidson_gen') result(rc)
+        import :: c_ptr, c_int, c_int32_t, c_int64_t, c_double
+        type(c_ptr), value :: A, B, pc
+        integer(c_int32_t), value :: k, ncv, max_steps
+        real(c_double), value :: tol
+        real(c_double), intent(in) :: q1(*)
+        real(c_double), intent(out) :: lambda(*), V(*), resid(*)
+        integer(c_int64_t), intent(out) :: info(7)
         integer(c_int), value :: where
         integer(c_int) :: rc
     end function
@@ -2102,6 +2116,60 @@ subroutine hip_davidson(A, k, lambda, pc, V, resid, ncv, tol, max_steps, q1, ste
     if (present(restarts)) restarts = int(info(4))
     if (present(found)) found = int(info(5))
     if (present(converged)) converged = info(6) /= 0
+end subroutine
+
+
+subroutine hip_davidson_gen(A, B, k, lambda, pc, V, resid, ncv, tol, max_steps, q1, steps, products, products_b, applies, restarts, &
+        & found, converged)
+    ! no reference counterpart: the k smallest eigenpairs of A x = lambda B x (A symmetric, B symmetric positive definite) by
+    ! hip_davidson's method in the B-inner product (sgm_davidson_gen; the contract is in include/sigma_hip.h): one product with
+    ! B per step, no solve with it.  pc (optional): a preconditioner that has been set up on A.  lambda(k); V(nrow, k)
+    ! (optional): V^T B V = I; resid(k) (optional): the TRUE |A v - lambda B v|_2.  Defaults as hip_davidson.
+    class(hip_matrix), intent(inout) :: A, B
+    integer, intent(in) :: k
+    real(dp), intent(out) :: lambda(:)
+    type(hip_linear_solver), intent(in), optional :: pc
+    real(dp), intent(out), optional :: V(:,:), resid(:)
+    integer, intent(in), optional :: ncv, max_steps
+    real(dp), intent(in), optional :: tol, q1(:)
+    integer, intent(out), optional :: steps, products, products_b, applies, restarts, found
+    logical, intent(out), optional :: converged
+    real(dp), allocatable :: q0(:), lc(:), Vc(:,:), rc(:)
+    integer(c_int64_t) :: info(7), i
+    integer :: m, ms
+    real(dp) :: t
+    type(c_ptr) :: hp
+    m = min(A%nrow - 1, max(2 * k + 1, 20))
+    ms = 1000
+    t = 1.0e-8_dp
+    if (present(ncv)) m = ncv
+    if (present(max_steps)) ms = max_steps
+    if (present(tol)) t = tol
+    hp = c_null_ptr
+    if (present(pc)) hp = pc%handle
+    allocate(q0(A%nrow), lc(max(k, 1)), Vc(A%nrow, max(k, 1)), rc(max(k, 1)))
+    if (present(q1)) then
+        q0 = q1
+    else
+        do i = 1, A%nrow
+            q0(i) = 1.0_dp + real(mod((i - 1) * 2654435761_c_int64_t, 1024_c_int64_t), dp) / 1024.0_dp
+        enddo
+    endif
+    Vc = 0.0_dp
+    call A%upload()
+    call B%upload()
+    call hip_check(sgm_davidson_gen(A%handle, B%handle, hp, int(k, c_int32_t), int(m, c_int32_t), t, int(ms, c_int32_t), q0, lc, Vc, &
+        & rc, info, SGM_HOST))
+    lambda(1:k) = lc(1:k)
+    if (present(V)) V(1:A%nrow, 1:k) = Vc(:, 1:k)
+    if (present(resid)) resid(1:k) = rc(1:k)
+    if (present(steps)) steps = int(info(1))
+    if (present(products)) products = int(info(2))
+    if (present(products_b)) products_b = int(info(3))
+    if (present(applies)) applies = int(info(4))
+    if (present(restarts)) restarts = int(info(5))
+    if (present(found)) found = int(info(6))
+    if (present(converged)) converged = info(7) /= 0
 end subroutine
 
 

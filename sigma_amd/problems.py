@@ -105,6 +105,26 @@ def poisson2d_csr(nx, ny):
                          (+1, i < nx - 1, -1.0), (+nx, j < ny - 1, -1.0)], 4.0, n)
 
 
+def fem2d_pair_csr(nx, ny):
+    """The stiffness / mass pair of the tensor P1 elements on the unit square, nx x ny interior nodes: with K1(n) = (1/h)
+    tridiag(-1, 2, -1), M1(n) = (h/6) tridiag(1, 4, 1), h = 1/(n+1):  A = Ky (x) Mx + My (x) Kx,  B = My (x) Mx.  Both 9-point,
+    columns ascending, 1-based.  Returns ((ptr, node, val) of A, (ptr, node, val) of B).  The eigenvalues of A x = lam B x are
+    kappa_i(nx) + kappa_j(ny), kappa_j(n) = 6 (1 - c_j) / (h^2 (2 + c_j)), c_j = cos(j pi h)."""
+    n = nx * ny
+    k = np.arange(n, dtype=np.int64)
+    i, j = k % nx, k // nx
+    hx, hy = 1.0 / (nx + 1), 1.0 / (ny + 1)
+    k1 = lambda d, h: 2.0 / h if d == 0 else -1.0 / h
+    m1 = lambda d, h: 4.0 * h / 6.0 if d == 0 else h / 6.0
+    sa, sb = [], []
+    for dj in (-1, 0, 1):
+        for di in (-1, 0, 1):
+            ok = (j + dj >= 0) & (j + dj < ny) & (i + di >= 0) & (i + di < nx)
+            sa.append((dj * nx + di, ok, k1(dj, hy) * m1(di, hx) + m1(dj, hy) * k1(di, hx)))
+            sb.append((dj * nx + di, ok, m1(dj, hy) * m1(di, hx)))
+    return _stencil_csr(sa, 0.0, n), _stencil_csr(sb, 0.0, n)
+
+
 def laplace3d_csr(nx, ny, nz):
     n = nx * ny * nz
     k = np.arange(n, dtype=np.int64)
