@@ -212,6 +212,28 @@ int sgm_ell_create(sgm_mat *out, int32_t nrow, int32_t ncol, int32_t max_d,
                    const int32_t *node_1based_colmajor, const double *val_colmajor,
                    int where);
 int sgm_ell_set_values(sgm_mat A, const double *val_colmajor, int where);
+/* ELLPACK degrees.  The reference keeps degrees(n) beside node(max_d,n): the first degrees(i) slots of row i are its entries,
+ * the rest is padding.  The products never read it (all max_d slots are summed); everything else does -- get_value / set_value /
+ * add_value and edit plans, add_sparse_matrix, the permutations, ILDU(0) and Jacobi setup (get_value scans the first degrees(i)
+ * slots and keeps the LAST hit, ellpack_matrices.f90:232-235), sgm_mat_get("degrees").
+ *
+ * sgm_ell_set_degrees hands the graph's own degrees in (host or device).  Checked before anything reads through them:
+ * 0 <= degrees(i) <= max_d and the first degrees(i) slots of row i hold columns of 1..ncol; a violation is SGM_ERR_DIMS and the
+ * handle keeps its previous degrees.  On success version and pattern_version move (which slots are entries has changed): an
+ * edit plan made before is refused, derived matrices and multigrid levels are rebuilt.
+ *
+ * Without that call sgm_ell_create recovers degrees from the padding, for three row shapes only:
+ *   d distinct nonzero columns, every later slot equal to slot d      (what add_edge / graph_build leave: ellpack_graphs.f90:164,394-397)
+ *   all slots 0                                                       (a row without edges; sgm_mat_get("node") gives the 0 back)
+ *   d distinct nonzero columns, every later slot 0                    (a caller's zero padding)
+ * If any row has another shape (say a column stored twice among a full row's slots) the handle holds NO degrees: the products
+ * work as ever, and every reader of degrees named above returns SGM_ERR_UNSUPPORTED with a message that names
+ * sgm_ell_set_degrees.
+ * LIMIT: the recovered degrees are right only for arrays no delete_edge has touched.  ellpack_delete_edge (ellpack_graphs.f90:
+ * 418-481) shifts the row left and copies the second-to-last slot into the last, so deleting the last neighbour of [a,b,c,c,c]
+ * (degree 3) leaves [a,b,c,c,c] with degree 2, and deleting the only neighbour of [a,a,a] leaves [a,a,a] with degree 0: rows
+ * that no rule can tell from add_edge rows of degree 3 and 1.  Graphs that have seen delete_edge must hand their degrees in. */
+int sgm_ell_set_degrees(sgm_mat A, const int32_t *degrees, int where);
 int sgm_mat_matvec(sgm_mat A, const double *x, double *y, int where);
 int sgm_mat_matvec_add(sgm_mat A, const double *x, double *y, int where);
 /* sgm_mat_matvec_dots: test introspection -- y = A x (add = 1: y += A x, not chained, like sgm_mat_matvec_add) launched with
@@ -871,9 +893,13 @@ int sgm_csr_create_dist_rect(sgm_mat *out, sgm_comm comm, const int64_t *row_sta
                              const int32_t *node_1based_global, const double *val, int where);
 /* sgm_ell_create_dist: this rank's rows of an ELLPACK matrix (node / val as (max_d, n_local) column-major,
  * GLOBAL 1-based columns, padding as the reference keeps it).  Held as fixed-length CSR rows whose padding
- * slots are stored entries, so the row sums equal ellpack_matvec_add's (ellpack_matrices.f90:640-665). */
+ * slots are stored entries, so the row sums equal ellpack_matvec_add's (ellpack_matrices.f90:640-665).
+ * degrees_or_null: this rank's degrees(n_local), where node / val live; checked like sgm_ell_set_degrees' (SGM_ERR_DIMS).
+ * NULL: recovered from the padding by the rule stated at sgm_ell_set_degrees, or absent when a row has another shape
+ * (ILDU(0) setup on the matrix then refuses). */
 int sgm_ell_create_dist(sgm_mat *out, sgm_comm comm, const int64_t *row_starts, int32_t max_d,
-                        const int32_t *node_1based_global_colmajor, const double *val_colmajor, int where);
+                        const int32_t *node_1based_global_colmajor, const double *val_colmajor,
+                        const int32_t *degrees_or_null, int where);
 int sgm_csr_create_partitioned(sgm_mat *out, int32_t nparts, const int64_t *row_starts /* nparts+1 */,
                                int32_t nrow, int32_t ncol, int64_t nnz,
                                const int32_t *ptr_1based, const int32_t *node_1based,
@@ -924,7 +950,8 @@ int sgm_partition_rows_by_nnz(int32_t nrow, const int32_t *ptr_1based, int32_t n
  * tools/asan) drives the statements the library runs:
  * sgm_ell_degrees_host        degrees(n) of an ELLPACK graph recovered from the padding the reference keeps (ellpack_graphs.f90:164,
  *                             :394-397: the rest of a row repeats the neighbour just added; a row of zeros is empty) -- what
- *                             sgm_ell_create / sgm_ell_create_dist do, since the product's interface carries no degrees
+ *                             sgm_ell_create / sgm_ell_create_dist do when no degrees are handed in; -1 for a row the padding
+ *                             does not describe (the rule and its limit: at sgm_ell_set_degrees above)
  * sgm_left_permute_rows_host  rows [r0, r1) (0-based) of A%left_permute(p) (cs_matrices.f90:471-478) cut out of the whole matrix:
  *                             what a rank keeps of a permuted matrix distributed over ranks.  lnode == NULL: sizing call. */
 int sgm_ell_degrees_host(int32_t n, int32_t max_d, const int32_t *node_1based_colmajor, int32_t *degrees_out);

@@ -86,6 +86,13 @@ interface   ! include/sigma_hip.h
         integer(c_int), value :: where
         integer(c_int) :: rc
     end function
+    function sgm_ell_set_degrees(A, degrees, where) bind(c, name='sgm_ell_set_degrees') result(rc)
+        import :: c_ptr, c_int, c_int32_t
+        type(c_ptr), value :: A
+        integer(c_int32_t), intent(in) :: degrees(*)
+        integer(c_int), value :: where
+        integer(c_int) :: rc
+    end function
     function sgm_ell_set_values(A, val, where) bind(c, name='sgm_ell_set_values') result(rc)
         import :: c_ptr, c_int, c_double
         type(c_ptr), value :: A
@@ -752,6 +759,8 @@ function hip_ell_device_handle(A) result(h)                                !
         if (c_associated(dev%handle)) call hip_check(sgm_mat_destroy(dev%handle), 'sgm_mat_destroy')
         call hip_check(sgm_ell_create(dev%handle, A%nrow, A%ncol, A%g%max_d, A%g%node, A%val, SGM_HOST), &
             & 'sgm_ell_create')
+        ! the graph's own degrees, always: after a delete_edge the padding no longer tells them (ellpack_graphs.f90:418-481)
+        if (A%nrow > 0) call hip_check(sgm_ell_set_degrees(dev%handle, A%g%degrees, SGM_HOST), 'sgm_ell_set_degrees')
     elseif (dev%values_stale) then
         call hip_check(sgm_ell_set_values(dev%handle, A%val, SGM_HOST), 'sgm_ell_set_values')
     endif

@@ -221,7 +221,37 @@ def comp_cases():
          rs.random_sample(n), [(CG, NOPC, 1e-14), (CG, JACOBI, 1e-14)], mode="comp:50", extra=dict(nb1=np.int32(50)))
 
 
+def ell_delete_case():
+    """ellpack_delete_edge (ellpack_graphs.f90:418-481, ref_driver mode `del:<file>`): a 12-vertex graph, then a list of
+    delete_edge calls -- a last neighbour, an only neighbour, a diagonal stored last, middle neighbours, an edge that is not
+    there, and the deletions that take the widest rows down so that the array shrinks.  The fixture holds the edge list, the
+    delete list and node / degrees / max_d as the reference leaves them; tests/test_ell_degrees_cpu.py holds the numpy
+    restatement (tests/ell_degree_cases.py) to it."""
+    name = "ell_delete_edge_12"
+    if ONLY and not name.startswith(ONLY):
+        return
+    n = 12
+    rows = {1: [1, 2, 3], 2: [2], 3: [2, 4, 3], 4: [4, 3, 5, 9, 1], 5: [5, 4, 6, 10, 12], 6: [6, 5, 7], 7: [], 8: [8, 7, 9, 1],
+            9: [9, 8, 10, 4], 10: [10, 9], 11: [3, 11], 12: [12, 5, 1, 2, 7]}
+    ei = np.array([i for i in sorted(rows) for _ in rows[i]], np.int32)
+    ej = np.array([j for i in sorted(rows) for j in rows[i]], np.int32)
+    dele = [(1, 3), (2, 2), (3, 3), (4, 3), (6, 6), (6, 12), (9, 10), (9, 4), (11, 3), (11, 11), (7, 1),
+            (4, 1), (5, 6), (12, 7), (12, 12), (8, 8)]
+    di, dj = np.array([d[0] for d in dele], np.int32), np.array([d[1] for d in dele], np.int32)
+    with tempfile.TemporaryDirectory() as td:
+        df = os.path.join(td, "del.bin")
+        with open(df, "wb") as f:
+            f.write(struct.pack("<i", len(di)) + di.astype("<i4").tobytes() + dj.astype("<i4").tobytes())
+        res = run_reference(n, n, ELL, (ei, ej, np.ones(len(ei))), np.zeros(n), np.zeros(n), [], mode="del:" + df)
+    res.update(n=np.int32(n), ei=ei, ej=ej, di=di, dj=dj)
+    os.makedirs(os.path.join(GOLDEN, "ell_degrees"), exist_ok=True)      # (a folder of its own: tests/golden/*.npz are matrix fixtures)
+    np.savez_compressed(os.path.join(GOLDEN, "ell_degrees", name + ".npz"), **res)
+
+
 if __name__ == "__main__":
+    ell_delete_case()
+    if ONLY and "ell_delete_edge_12".startswith(ONLY):
+        sys.exit(0)
     main()
     perm_cases()
     eig_cases()

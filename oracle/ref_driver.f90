@@ -21,6 +21,11 @@
 ! `matvec_seconds_each=` / `solve ... seconds=` lines (bench.py's           !
 ! cpu_baseline of kind "reference").                                       !
 !                                                                          !
+! With `del:<file>` (fmt = 2 only) the driver stops after the graph: the   !
+! ellpack_graph built from the edge list gets the delete_edge calls of     !
+! <file> (stream: nd, di(nd), dj(nd)) in order, and node / degrees / max_d !
+! are dumped as they then stand (ellpack_graphs.f90:418-481).              !
+!                                                                          !
 ! Problem file (unformatted stream, int32 / float64):                      !
 !   n, m, ne, fmt(1=csr,2=ellpack), nsolve                                  !
 !   ei(ne), ej(ne)      edges in INSERTION order (1-based)                  !
@@ -45,7 +50,9 @@ use eigensolver
 implicit none
 
     character(len=512) :: infile, outprefix, mode
-    logical :: timing, perm_mode, eig_mode, comp_mode
+    logical :: timing, perm_mode, eig_mode, comp_mode, del_mode
+    integer :: nd
+    integer, allocatable :: di(:), dj(:)
     integer :: nb1, it, jt, bi, bj, r0(3), nbe
     type(sparse_matrix), target :: Scomp
     class(graph_interface), pointer :: gb
@@ -75,10 +82,12 @@ implicit none
     perm_mode = .false.
     eig_mode = .false.
     comp_mode = .false.
+    del_mode = .false.
     reps = 0
     if (command_argument_count() >= 3) then
         call getarg(3, mode)
         if (mode(1:4) == 'perm') perm_mode = .true.
+        if (mode(1:4) == 'del:') del_mode = .true.
         if (mode(1:5) == 'comp:') then
             comp_mode = .true.
             read(mode(6:), *) nb1
@@ -123,6 +132,26 @@ implicit none
     do k = 1, ne
         call g%add_edge(ei(k), ej(k))
     enddo
+
+    if (del_mode .and. fmt == 2) then
+        call convert_graph_type(g, "ellpack")
+        open(unit=23, file=trim(mode(5:)), access='stream', form='unformatted', status='old')
+        read(23) nd
+        allocate(di(nd), dj(nd))
+        read(23) di
+        read(23) dj
+        close(23)
+        do k = 1, nd
+            call g%delete_edge(di(k), dj(k))
+        enddo
+        select type(g)
+            type is(ellpack_graph)
+                call dump_i4('del_max_d', [g%max_d], 1)
+                call dump_i4('del_degrees', g%degrees, size(g%degrees))
+                call dump_i4('del_node', reshape(g%node, [size(g%node)]), size(g%node))
+        end select
+        stop
+    endif
 
     if (fmt == 1) then
         call convert_graph_type(g, "compressed sparse")

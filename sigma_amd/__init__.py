@@ -451,9 +451,18 @@ class _Matrix:
         """`nrow ncol nnz`, then one `i j value` line per stored entry in stored order (rows in
         order, a row's entries as they lie in memory); `trans` swaps i/j and the dimensions like the
         reference.  Values are written with 17 significant digits (they read back bit for bit)."""
-        if not isinstance(self, csr_matrix):
-            raise SigmaError(7, "to_file: CSR matrices only")
-        ptr, node, val = self.get("ptr", np.int32), self.get("node", np.int32), self.get("val", np.float64)
+        if isinstance(self, ellpack_matrix):
+            # the reference's edge cursor hands out the first degrees(i) slots of every row (ellpack_graphs.f90:310-369); a matrix
+            # without degrees refuses here (get("degrees"))
+            deg = self.get("degrees", np.int32)
+            keep = np.arange(self.max_d)[None, :] < deg[:, None]
+            node = self.get("node", np.int32).reshape(self.nrow, self.max_d)[keep]
+            val = self.get("val", np.float64).reshape(self.nrow, self.max_d)[keep]
+            ptr = np.concatenate([[0], np.cumsum(deg, dtype=np.int64)])
+        elif isinstance(self, csr_matrix):
+            ptr, node, val = self.get("ptr", np.int32), self.get("node", np.int32), self.get("val", np.float64)
+        else:
+            raise SigmaError(7, "to_file: CSR and ELLPACK matrices only")
         rows = np.repeat(np.arange(1, self.nrow + 1, dtype=np.int64), np.diff(ptr))
         a, b = (node, rows) if trans else (rows, node)
         dims = (self.ncol, self.nrow) if trans else (self.nrow, self.ncol)
@@ -669,9 +678,10 @@ class dist_csr_matrix(_Matrix):
 
 class dist_ellpack_matrix(_Matrix):
     """This rank's rows of an ELLPACK matrix partitioned over processes (sgm_ell_create_dist): node / val
-    as C arrays of shape (n_local, max_d) = the reference's (max_d, n_local), GLOBAL 1-based columns."""
+    as C arrays of shape (n_local, max_d) = the reference's (max_d, n_local), GLOBAL 1-based columns; degrees: this rank's
+    degrees(n_local), where node / val live (None: recovered from the padding, see ellpack_matrix)."""
 
-    def __init__(self, comm, row_starts, node_global, val):
+    def __init__(self, comm, row_starts, node_global, val, degrees=None):
         super().__init__()
         rs = np.ascontiguousarray(row_starts, np.int64)
         max_d = int(node_global.shape[1])
@@ -680,8 +690,9 @@ class dist_ellpack_matrix(_Matrix):
         self.nrow = self.ncol = int(rs[-1])
         self.n_local = self.nc_local = int(rs[comm.rank + 1] - rs[comm.rank])
         self.max_d = max_d
-        _ck(lib().sgm_ell_create_dist(C.byref(self._h), comm._h, C.c_void_p(rs.ctypes.data), C.c_int32(max_d), pn, pv,
-                                      C.c_int(_same_where(w1, w2))))
+        pd, w3, _k3 = (None, w1, None) if degrees is None else _arg(degrees, np.int32)
+        _ck(lib().sgm_ell_create_dist(C.byref(self._h), comm._h, C.c_void_p(rs.ctypes.data), C.c_int32(max_d), pn, pv, pd,
+                                      C.c_int(_same_where(w1, w2, w3))))
 
 
 class sparse_matrix(_Matrix):
@@ -738,9 +749,13 @@ class sparse_matrix(_Matrix):
 
 class ellpack_matrix(_Matrix):
     """ellpack_matrix (ellpack_matrices.f90:28-105): node(max_d,n), val(max_d,n) in Fortran
-    order, i.e. a C array of shape (n, max_d); padding = last neighbour / 0.0."""
+    order, i.e. a C array of shape (n, max_d); padding = last neighbour / 0.0.
+    degrees: the graph's degrees(n) -- the first degrees(i) slots of row i are its entries (sgm_ell_set_degrees).  None: recovered
+    from the padding for add_edge-shaped, all-zero and zero-padded rows; if any row has another shape the matrix holds no degrees,
+    its products work and every reader of degrees raises SigmaError 8.  Arrays a delete_edge has touched need `degrees`
+    (include/sigma_hip.h states why)."""
 
-    def __init__(self, nrow, ncol, node, val):
+    def __init__(self, nrow, ncol, node, val, degrees=None):
         super().__init__()
         if _is_torch(node):
             max_d = int(node.shape[1])
@@ -753,6 +768,22 @@ class ellpack_matrix(_Matrix):
         self.nrow, self.ncol, self.max_d = int(nrow), int(ncol), max_d
         _ck(lib().sgm_ell_create(C.byref(self._h), C.c_int32(nrow), C.c_int32(ncol), C.c_int32(max_d), pn, pv,
                                  C.c_int(_same_where(w1, w2))))
+        if degrees is not None:
+            try:
+                self.set_degrees(degrees)
+            except SigmaError:
+                self.destroy()
+                raise
+
+    def set_degrees(self, degrees):
+        """sgm_ell_set_degrees: degrees(nrow), checked (SigmaError 2 and the previous degrees kept on a violation); plans and
+        derived matrices made before are refused or rebuilt afterwards."""
+        if not _is_torch(degrees):
+            degrees = np.ascontiguousarray(degrees, np.int32)
+        if _len(degrees) != self.nrow:
+            raise SigmaError(2, f"set_degrees: {_len(degrees)} degrees for {self.nrow} rows")
+        pd, w, _k = _arg(degrees, np.int32)
+        _ck(lib().sgm_ell_set_degrees(self._h, pd, C.c_int(w)))
 
     def set_values(self, val):
         pv, w, _k = _arg(val, np.float64)
@@ -1488,7 +1519,8 @@ def partition_rows_by_nnz(ptr, nparts, align=512):
 
 def ell_degrees_host(node):
     """sgm_ell_degrees_host: degrees(n) of an ELLPACK graph (node as (n, max_d) = the reference's (max_d, n), 1-based) recovered
-    from the padding the reference keeps -- what sgm_ell_create does, since the product's interface carries no degrees."""
+    from the padding the reference keeps -- what sgm_ell_create does when no degrees are handed in; -1 for a row the padding
+    does not describe (a handle with such a row holds no degrees at all)."""
     node = np.ascontiguousarray(node, np.int32)
     n, md = node.shape
     deg = np.zeros(max(n, 1), np.int32)

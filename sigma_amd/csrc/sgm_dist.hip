@@ -908,9 +908,11 @@ int sgm_csr_create_dist_rect(sgm_mat *out, sgm_comm comm, const int64_t *row_sta
  * are stored entries (value 0.0, column = the row's last neighbour), so the row sums -- and a 0 * Inf in a
  * padding slot -- come out exactly as the reference's.  node / val: (max_d, n_local) column-major like the
  * reference holds them, GLOBAL 1-based columns.  A slot of an empty row (node 0 in the reference, which then
- * reads x(0)) points at the row's own column. */
+ * reads x(0)) points at the row's own column.
+ * degrees: this rank's degrees(n_local) (host or device like node), or null = recovered from the padding where the padding
+ * tells them (sgm_plan_host.hpp); a row it does not describe leaves the part without degrees, and ILDU(0) setup refuses. */
 int sgm_ell_create_dist(sgm_mat *out, sgm_comm comm, const int64_t *row_starts, int32_t max_d, const int32_t *node,
-                        const double *val, int where)
+                        const double *val, const int32_t *degrees, int where)
 {
     SGM_TRY(require_init());
     if (!out || !comm || !row_starts || max_d < 0) return fail(SGM_ERR_BAD_ARG, "sgm_ell_create_dist: bad argument");
@@ -931,12 +933,25 @@ int sgm_ell_create_dist(sgm_mat *out, sgm_comm comm, const int64_t *row_starts, 
     // degrees(i), recovered from the padding the reference keeps (k_ell_degrees, sgm_mat.hip): what an ILDU(0) setup on these
     // rows goes by -- the reference's pattern pass and fill read the real entries only (ellpack_graphs.f90:310-369)
     std::vector<int32_t> hdeg((size_t)std::max(n, 1), 0);
-    SGM_TRY(host_ell_degrees_host(n, max_d, hnode.data(), hdeg.data()));
+    bool have_deg = true;
+    if (degrees) {
+        if (n) SGM_HIP(hipMemcpy(hdeg.data(), degrees, (size_t)n * 4, where == SGM_HOST ? hipMemcpyHostToHost : hipMemcpyDeviceToHost));
+        for (int32_t i = 0; i < n; ++i) {
+            bool ok = hdeg[i] >= 0 && hdeg[i] <= max_d;
+            for (int32_t k = 0; ok && k < hdeg[i]; ++k) ok = hnode[(size_t)i * max_d + k] >= 1 && hnode[(size_t)i * max_d + k] <= row_starts[comm->nranks];
+            if (!ok) return fail(SGM_ERR_DIMS, "sgm_ell_create_dist: degrees(%d) = %d: outside 0..%d, or one of the first %d slots of that row holds no column",
+                                 i + 1, hdeg[i], max_d, hdeg[i]);
+        }
+    } else {
+        SGM_TRY(host_ell_degrees_host(n, max_d, hnode.data(), hdeg.data()));
+        for (int32_t i = 0; i < n; ++i) have_deg = have_deg && hdeg[i] >= 0;
+    }
     for (int32_t i = 0; i < n; ++i)
         for (int32_t k = 0; k < max_d; ++k)
             if (hnode[(size_t)i * max_d + k] <= 0) hnode[(size_t)i * max_d + k] = (int32_t)(r0 + i + 1);
     SGM_TRY(sgm_csr_create_dist(out, comm, row_starts, nnz, hptr.data(), hnode.data(), hval.data(), SGM_HOST));
     Part &p = (*out)->parts[0];
+    if (!have_deg) return SGM_OK;
     SGM_TRY(dalloc(&p.edeg, (size_t)std::max(n, 1)));
     SGM_HIP(hipMemcpyAsync(p.edeg, hdeg.data(), (size_t)std::max(n, 1) * 4, hipMemcpyHostToDevice, g_rt.stream));
     SGM_HIP(hipStreamSynchronize(g_rt.stream));

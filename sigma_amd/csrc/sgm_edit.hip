@@ -40,7 +40,7 @@ struct EditSrc {
 struct EditRow { int64_t first, stride; int32_t steps; };
 __device__ inline EditRow edit_row(const EditSrc &s, int32_t i)
 {
-    if (s.ell) return EditRow{i, s.n, s.edeg ? s.edeg[i] : 0};
+    if (s.ell) return EditRow{i, s.n, s.edeg ? s.edeg[i] : 0};      // (no edeg: a matrix without slots, check_leaf saw to it)
     const int32_t lo = s.rowptr[i];
     return EditRow{lo, 1, s.rowptr[i + 1] - lo};
 }
@@ -275,12 +275,14 @@ struct Scratch {
 };
 static int bits_for(int64_t v) { int b = 1; while (b < 32 && (1ll << b) <= v) ++b; return b; }
 
-static int check_leaf(const char *fn, sgm_mat A, const char *which = "A")
+// degrees: the call goes by an ELLPACK operand's degrees (every one but zero / scalar_multiply, which touch all slots alike)
+static int check_leaf(const char *fn, sgm_mat A, const char *which = "A", bool degrees = true)
 {
     if (!A) return fail(SGM_ERR_BAD_ARG, "%s: null matrix %s", fn, which);
     if (A->fmt == SGM_FMT_COMPOSITE) return fail(SGM_ERR_UNSUPPORTED, "%s: %s is a composite matrix (single-GPU CSR / ELLPACK leaves only)", fn, which);
     if (A->distributed()) return fail(SGM_ERR_UNSUPPORTED, "%s: %s is distributed / partitioned (single-GPU CSR / ELLPACK leaves only)", fn, which);
     if (A->fmt != SGM_FMT_CSR && A->fmt != SGM_FMT_ELL) return fail(SGM_ERR_UNSUPPORTED, "%s: unknown matrix format", fn);
+    if (degrees && A->fmt == SGM_FMT_ELL) SGM_TRY(ell_need_degrees(fn, A->parts[0]));      // (never read as degree 0)
     return SGM_OK;
 }
 static int64_t slots_of(sgm_mat A) { const Part &p = A->parts[0]; return A->fmt == SGM_FMT_ELL ? (int64_t)p.n * p.max_d : p.nnz; }
@@ -576,7 +578,7 @@ int sgm_mat_get_entries(sgm_mat A, int64_t m, const int32_t *i, const int32_t *j
 static int scale_all(const char *fn, sgm_mat A, double alpha, int zero)
 {
     SGM_TRY(require_init());
-    SGM_TRY(check_leaf(fn, A));
+    SGM_TRY(check_leaf(fn, A, "A", false));
     SGM_TRY(open_arrays(A, zero != 0));
     const int64_t n = slots_of(A);
     if (n > 0) hipLaunchKernelGGL(k_edit_scale, dim3(vec_grid(n)), dim3(kBlock), 0, g_rt.stream, n, values_of(A), alpha, zero);
@@ -655,7 +657,7 @@ int sgm_edit_plan_apply(sgm_edit_plan plan, sgm_mat A, const double *z, int mode
     SGM_TRY(check_batch(fn, plan->m, z, z, z, where));
     if (A->serial != plan->serial) return fail(SGM_ERR_BAD_ARG, "%s: the matrix is not the one the plan was created for", fn);
     if (A->pattern_version != plan->pattern_version)
-        return fail(SGM_ERR_BAD_ARG, "%s: the matrix's pattern changed since the plan was created (permuted)", fn);
+        return fail(SGM_ERR_BAD_ARG, "%s: the matrix's pattern changed since the plan was created (permuted, or its ELLPACK degrees set)", fn);
     Batch b;
     SGM_TRY(to_device(b.s, z, plan->m, where, &b.z));
     // every slot rewritten from +0.0 or from z: the old values are not read, a lean handle needs only a buffer

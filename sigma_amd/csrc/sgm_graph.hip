@@ -229,7 +229,8 @@ int sgm_ell_from_edges(sgm_mat *out, int32_t nrow, int32_t ncol, int64_t ne, con
                            (const int32_t *)ptr, (const int32_t *)node, (const double *)val, enode, eval, deg);
     if (rc == SGM_OK) rc = sgm_ell_create(out, nrow, ncol, max_d, enode, eval, SGM_DEVICE);
     if (rc == SGM_OK) {
-        (*out)->parts[0].edeg = deg;           // kept for sgm_mat_get("degrees")
+        dfree((*out)->parts[0].edeg);          // the graph's own degrees replace the ones recovered from the padding
+        (*out)->parts[0].edeg = deg;
         deg = nullptr;
     }
     dfree(ptr); dfree(node); dfree(val); dfree(dmax); dfree(enode); dfree(eval); dfree(deg);

@@ -1021,7 +1021,8 @@ int real_entries_as_csr(const Part &p, bool ell, Part &v)
 {
     hipStream_t st = g_rt.stream;
     const int32_t n = p.n;
-    if (!p.edeg && n && (!ell || p.max_d)) return fail(SGM_ERR_UNSUPPORTED, "ILDU(0) on an ELLPACK matrix needs its degrees (this handle has none)");
+    if (ell) SGM_TRY(ell_need_degrees("ILDU(0) setup", p));
+    else if (!p.edeg && n) return fail(SGM_ERR_UNSUPPORTED, "ILDU(0) on ELLPACK rows over ranks needs their degrees (this handle has none: sgm_ell_create_dist takes them)");
     v.n = n;
     v.ncol_own = p.ncol_own;
     v.n_halo = p.n_halo;

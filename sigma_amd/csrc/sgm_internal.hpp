@@ -235,7 +235,10 @@ struct Part {
     int32_t max_d = 0;
     int32_t *ecol = nullptr;
     double *eval = nullptr;
-    int32_t *edeg = nullptr;       // degrees(n), only when built by sgm_ell_from_edges
+    int32_t *edeg = nullptr;       // degrees(n): handed in (sgm_ell_set_degrees, sgm_ell_from_edges) or recovered from the padding;
+                                   // null on a handle whose rows the padding cannot describe (ell_need_degrees refuses its readers)
+    uint8_t *ezero = nullptr;      // slot-major, 1 where the caller's node was 0 (ecol holds the clamped column 0 there for the
+                                   // product's sake); null when no slot was 0.  Read by get("node") and the permutations only.
     uint8_t *ecode = nullptr;      // ELLPACK offset-dictionary codes, row-major n x emdp (emdp = max_d rounded up)
     int32_t emdp = 0;
     // column-blocked two-phase form of an ELLPACK matrix with random columns (sgm_ellcb.hip)
@@ -414,6 +417,14 @@ int rebuild_csr_formats(Part &p);
 int rebuild_ell_formats(Part &p);
 void free_part(Part &p);
 int sgm_invalidate_transpose(sgm_mat A);
+// What every reader of an ELLPACK part's degrees starts with: a part whose rows the padding could not describe (no edeg, and
+// slots to describe) is refused, never read as degree 0 or max_d.  The products do not come here.
+inline int ell_need_degrees(const char *fn, const Part &p)
+{
+    if (p.edeg || !p.n || !p.max_d) return SGM_OK;
+    return fail(SGM_ERR_UNSUPPORTED, "%s: this ELLPACK matrix holds no degrees (a row's padding does not tell its real entries): "
+                                     "hand them in with sgm_ell_set_degrees", fn);
+}
 // sgm_spmv.hip: the interior rows [int_lo, int_hi) of a part with a halo, from its 1-based host pattern
 void set_interior_range(Part &p, const int32_t *ptr1, const int32_t *node1);
 // sgm_dist.hip: permutations and the graph of a matrix distributed over ranks (the graph gathered onto every rank, rows

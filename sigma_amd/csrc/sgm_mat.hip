@@ -2,6 +2,7 @@
 // getters, and the staging of caller vectors.
 #include "sgm_spmv_select.hpp"
 #include "sgm_krylov.hpp"      // k_reduce: the reducer the consumers of a fused dot use (sgm_mat_matvec_dots)
+#include "sgm_plan_host.hpp"   // the rule that recovers ELLPACK degrees from the padding (k_ell_degrees)
 
 namespace sgm {
 
@@ -365,20 +366,44 @@ int sgm_csr_set_values(sgm_mat A, const double *val, int where)
     return SGM_OK;
 }
 
-// degrees(i) of an ELLPACK row as the reference holds it (ellpack_graphs.f90:14-21): add_edge / graph_build set the whole rest
-// of the row to the neighbour just added (`g%node(d+1:, i) = j`, :164,:394-397) and never store a neighbour twice, so the last
-// slot holds the last real neighbour and its FIRST occurrence is slot degrees(i); an empty row keeps node(:, i) = 0.
+// degrees(i) of an ELLPACK row recovered from its padding, or -1 where the padding does not describe the row: the rule and its
+// limit are stated once, at host_ell_degrees_host (sgm_plan_host.hpp); unknown[0] = 1 when any row is -1.
+__device__ inline int32_t ell_row_degree(const int32_t *__restrict__ row, int32_t max_d) { SGM_ELL_ROW_DEGREE_BODY }
 __global__ void k_ell_degrees(int32_t n, int32_t max_d, const int32_t *__restrict__ node /* (max_d, n) as handed over, 1-based */,
-                              int32_t *__restrict__ deg)
+                              int32_t *__restrict__ deg, int32_t *__restrict__ unknown)
 {
     const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const int32_t *row = node + (int64_t)i * max_d;
-    const int32_t last = row[max_d - 1];
-    int32_t d = 0;
-    if (last != 0)
-        for (d = 1; d < max_d && row[d - 1] != last; ++d) {}
+    const int32_t d = ell_row_degree(node + (int64_t)i * max_d, max_d);
     deg[i] = d;
+    if (d < 0) unknown[0] = 1;
+}
+// ezero[slot-major] = 1 where the caller's node is 0 (the reference's marker of an unused slot: ellpack_graphs.f90:535 keeps it
+// through right_permute); flags[1] = 1 when there is one.  node: (max_d, n) as handed over.
+__global__ void k_ell_zero_slots(int32_t n, int32_t max_d, const int32_t *__restrict__ node, uint8_t *__restrict__ ezero,
+                                 int32_t *__restrict__ flags)
+{
+    int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t total = (int64_t)n * max_d, stride = (int64_t)gridDim.x * blockDim.x;
+    for (; t < total; t += stride) {
+        const int32_t k = (int32_t)(t / n), i = (int32_t)(t % n);
+        const bool z = node[(int64_t)i * max_d + k] == 0;
+        ezero[t] = z ? 1 : 0;
+        if (z) flags[1] = 1;
+    }
+}
+// sgm_ell_set_degrees: bad[0] = smallest row whose degree is outside 0..max_d or whose first deg(i) slots hold a 0 marker
+// (every other slot holds a column of 1..ncol since sgm_ell_create).  Reads deg only; nothing is indexed through it unchecked.
+__global__ void k_ell_check_degrees(int32_t n, int32_t max_d, const int32_t *__restrict__ deg, const uint8_t *__restrict__ ezero,
+                                    unsigned long long *__restrict__ bad)
+{
+    const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int32_t d = deg[i];
+    bool ok = d >= 0 && d <= max_d;
+    if (ok && ezero)
+        for (int32_t k = 0; k < d; ++k) ok = ok && !ezero[(int64_t)k * n + i];
+    if (!ok) atomicMin(bad, (unsigned long long)i);
 }
 
 int sgm_ell_create(sgm_mat *out, int32_t nrow, int32_t ncol, int32_t max_d, const int32_t *node,
@@ -417,14 +442,24 @@ int sgm_ell_create(sgm_mat *out, int32_t nrow, int32_t ncol, int32_t max_d, cons
     }
     hipLaunchKernelGGL(k_ell_transpose, dim3(vec_grid(total)), dim3(kBlock), 0, g_rt.stream, src, (const double *)nullptr, p.ecol,
                        p.eval, nrow, max_d, ncol, bad);
-    // degrees(n): not an argument (the product never reads it, ellpack_matrices.f90:640-665), but what the reference's edge
-    // cursor and get_value go by (ellpack_graphs.f90:310-369) -- recovered from the padding the reference keeps
+    // degrees(n): not an argument here (the product never reads it, ellpack_matrices.f90:640-665), but what the reference's edge
+    // cursor and get_value go by (ellpack_graphs.f90:310-369) -- recovered from the padding where the padding tells them
+    // (sgm_plan_host.hpp), absent otherwise until sgm_ell_set_degrees hands them in
+    int32_t *flags = nullptr, hflags[2] = {0, 0};           // [0]: a row the padding does not describe, [1]: a slot that is 0
+    SGM_TRY(dalloc(&flags, 2));
+    SGM_HIP(hipMemsetAsync(flags, 0, 2 * sizeof(int32_t), g_rt.stream));
     SGM_TRY(dalloc(&p.edeg, (size_t)nrow));
-    hipLaunchKernelGGL(k_ell_degrees, dim3((nrow + kBlock - 1) / kBlock), dim3(kBlock), 0, g_rt.stream, nrow, max_d, src, p.edeg);
+    SGM_TRY(dalloc(&p.ezero, total));
+    hipLaunchKernelGGL(k_ell_degrees, dim3((nrow + kBlock - 1) / kBlock), dim3(kBlock), 0, g_rt.stream, nrow, max_d, src, p.edeg, flags);
+    hipLaunchKernelGGL(k_ell_zero_slots, dim3(vec_grid(total)), dim3(kBlock), 0, g_rt.stream, nrow, max_d, src, p.ezero, flags);
     SGM_HIP(hipMemcpyAsync(&hbad, bad, sizeof hbad, hipMemcpyDeviceToHost, g_rt.stream));
+    SGM_HIP(hipMemcpyAsync(hflags, flags, sizeof hflags, hipMemcpyDeviceToHost, g_rt.stream));
     SGM_HIP(hipStreamSynchronize(g_rt.stream));
     dfree(tn);
     dfree(bad);
+    dfree(flags);
+    if (hflags[0]) { dfree(p.edeg); p.edeg = nullptr; }
+    if (!hflags[1]) { dfree(p.ezero); p.ezero = nullptr; }
     if (hbad != ~0ull) {
         int32_t c = 0;
         const int64_t e = (int64_t)hbad;        // entry (slot k, row i) of the (max_d, n) array: e = i * max_d + k
@@ -462,6 +497,48 @@ int sgm_ell_set_values(sgm_mat A, const double *val, int where)
     SGM_TRY(refresh_ell_colblock_values(p));
     SGM_HIP(hipStreamSynchronize(g_rt.stream));
     dfree(tv);
+    return SGM_OK;
+}
+
+/* sgm_ell_set_degrees: degrees(n) of the graph behind a single-GPU ELLPACK matrix, as the caller holds them -- which slots of
+ * a row are real entries is the caller's knowledge, the padding only hints at it (sgm_plan_host.hpp).  Checked before anything
+ * reads through them: 0 <= degrees(i) <= max_d, and the first degrees(i) slots of row i hold columns (1..ncol, not the 0
+ * marker).  A violation is SGM_ERR_DIMS and the handle keeps what it had.  Which slots are entries changes, so version and
+ * pattern_version move: edit plans and derived matrices made before are refused or rebuilt like after a permutation. */
+int sgm_ell_set_degrees(sgm_mat A, const int32_t *degrees, int where)
+{
+    SGM_TRY(require_init());
+    if (!A || A->fmt != SGM_FMT_ELL || A->distributed() || (A->nrow && !degrees) || (where != SGM_HOST && where != SGM_DEVICE))
+        return fail(SGM_ERR_BAD_ARG, "sgm_ell_set_degrees: a single-GPU ELLPACK matrix and its degrees(nrow)");
+    Part &p = A->parts[0];
+    const int32_t n = p.n;
+    hipStream_t st = g_rt.stream;
+    int32_t *deg = nullptr;
+    unsigned long long *bad = nullptr, hbad = ~0ull;
+    SGM_TRY(dalloc(&deg, (size_t)std::max(n, 1)));
+    int rc = dalloc(&bad, 1);
+    if (rc == SGM_OK && hipMemsetAsync(bad, 0xff, sizeof hbad, st) != hipSuccess) rc = fail(SGM_ERR_HIP, "sgm_ell_set_degrees: memset");
+    if (rc == SGM_OK && n &&
+        hipMemcpyAsync(deg, degrees, (size_t)n * 4, where == SGM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st) != hipSuccess)
+        rc = fail(SGM_ERR_HIP, "sgm_ell_set_degrees: copy of degrees");
+    if (rc == SGM_OK && n)
+        hipLaunchKernelGGL(k_ell_check_degrees, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, n, p.max_d, (const int32_t *)deg,
+                           (const uint8_t *)p.ezero, bad);
+    if (rc == SGM_OK && (hipMemcpyAsync(&hbad, bad, sizeof hbad, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                         hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess))
+        rc = fail(SGM_ERR_HIP, "sgm_ell_set_degrees: check kernel failed");
+    dfree(bad);
+    if (rc == SGM_OK && hbad != ~0ull) {
+        int32_t d = 0;
+        (void)hipMemcpy(&d, deg + hbad, 4, hipMemcpyDeviceToHost);
+        rc = fail(SGM_ERR_DIMS, "sgm_ell_set_degrees: degrees(%lld) = %d: outside 0..%d, or one of the first %d slots of that row holds no column",
+                  (long long)hbad + 1, d, p.max_d, d);
+    }
+    if (rc != SGM_OK) { dfree(deg); return rc; }
+    dfree(p.edeg);
+    p.edeg = deg;
+    A->version += 1;
+    A->pattern_version += 1;
     return SGM_OK;
 }
 
@@ -628,17 +705,21 @@ int sgm_mat_get(sgm_mat A, const char *name, void *out, size_t bytes, size_t *ne
         if (p.nnz) SGM_HIP(hipMemcpy(vd.data(), p.val, vd.size() * 8, hipMemcpyDeviceToHost));
     } else if (ell && nm == "max_d") {
         vi.assign(1, p.max_d);
-    } else if (ell && nm == "degrees" && p.edeg) {
-        vi.resize((size_t)p.n);
-        if (p.n) SGM_HIP(hipMemcpy(vi.data(), p.edeg, vi.size() * 4, hipMemcpyDeviceToHost));
+    } else if (ell && nm == "degrees") {
+        SGM_TRY(ell_need_degrees("sgm_mat_get(\"degrees\")", p));
+        vi.assign((size_t)p.n, 0);                        // (no slots: every degree is 0)
+        if (p.n && p.edeg) SGM_HIP(hipMemcpy(vi.data(), p.edeg, vi.size() * 4, hipMemcpyDeviceToHost));
     } else if (ell && (nm == "node" || nm == "val")) {
         const size_t total = (size_t)p.n * p.max_d;       // back to the reference's (max_d, n) order
         if (nm == "node") {
             std::vector<int32_t> t(total);
+            std::vector<uint8_t> z(p.ezero ? total : 0);   // the slots the caller handed in as 0 read back as 0
             if (total) SGM_HIP(hipMemcpy(t.data(), p.ecol, total * 4, hipMemcpyDeviceToHost));
+            if (!z.empty()) SGM_HIP(hipMemcpy(z.data(), p.ezero, total, hipMemcpyDeviceToHost));
             vi.resize(total);
             for (int32_t i = 0; i < p.n; ++i)
-                for (int32_t k = 0; k < p.max_d; ++k) vi[(size_t)i * p.max_d + k] = t[(size_t)k * p.n + i] + 1;
+                for (int32_t k = 0; k < p.max_d; ++k)
+                    vi[(size_t)i * p.max_d + k] = !z.empty() && z[(size_t)k * p.n + i] ? 0 : t[(size_t)k * p.n + i] + 1;
         } else {
             std::vector<double> t(total);
             if (total) SGM_HIP(hipMemcpy(t.data(), p.eval, total * 8, hipMemcpyDeviceToHost));
@@ -728,6 +809,7 @@ static int64_t part_resident_bytes(const Part &p)
     if (p.ecol) b += 4 * (int64_t)p.n * p.max_d;
     if (p.eval) b += 8 * (int64_t)p.n * p.max_d;
     if (p.edeg) b += 4 * (int64_t)p.n;
+    if (p.ezero) b += (int64_t)p.n * p.max_d;
     if (p.ecode) b += (int64_t)p.n * p.emdp;
     if (p.xext) b += 8 * p.xlen();
     b += ell_colblock_resident_bytes(p);

@@ -151,8 +151,9 @@ __global__ void k_perm_cols(int64_t nnz, int32_t *__restrict__ col, const int32_
 }
 // ELLPACK, slot-major device layout (slot k of row i at k*n + i): row i -> row p(i) in every slot
 __global__ void k_ell_perm_rows(int32_t n, int32_t max_d, const int32_t *__restrict__ p1, const int32_t *__restrict__ ecol,
-                                const double *__restrict__ eval, const int32_t *__restrict__ edeg,
-                                int32_t *__restrict__ ecol2, double *__restrict__ eval2, int32_t *__restrict__ edeg2)
+                                const double *__restrict__ eval, const int32_t *__restrict__ edeg, const uint8_t *__restrict__ ezero,
+                                int32_t *__restrict__ ecol2, double *__restrict__ eval2, int32_t *__restrict__ edeg2,
+                                uint8_t *__restrict__ ezero2)
 {
     const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -160,15 +161,18 @@ __global__ void k_ell_perm_rows(int32_t n, int32_t max_d, const int32_t *__restr
     for (int32_t k = 0; k < max_d; ++k) {
         ecol2[(int64_t)k * n + d] = ecol[(int64_t)k * n + i];
         eval2[(int64_t)k * n + d] = eval[(int64_t)k * n + i];
+        if (ezero) ezero2[(int64_t)k * n + d] = ezero[(int64_t)k * n + i];
     }
     if (edeg) edeg2[d] = edeg[i];
 }
-// ellpack_graph_right_permute: every real neighbour j -> p(j) (a 0 in the reference = -1 here stays)
-__global__ void k_ell_perm_cols(int64_t total, int32_t *__restrict__ ecol, const int32_t *__restrict__ p1)
+// ellpack_graph_right_permute: every neighbour j -> p(j); a 0 of the reference (ezero here, the stored column clamped to 0 for
+// the product) stays what it is (ellpack_graphs.f90:535)
+__global__ void k_ell_perm_cols(int64_t total, int32_t *__restrict__ ecol, const uint8_t *__restrict__ ezero, const int32_t *__restrict__ p1)
 {
     int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (; k < total; k += stride) { const int32_t c = ecol[k]; if (c >= 0) ecol[k] = p1[c] - 1; }
+    for (; k < total; k += stride)
+        if (!ezero || !ezero[k]) ecol[k] = p1[ecol[k]] - 1;
 }
 __global__ void k_check_perm(int32_t n, const int32_t *__restrict__ p1, int32_t *__restrict__ seen, int *bad)
 {
@@ -862,6 +866,7 @@ int sgm_mat_left_permute(sgm_mat A, const int32_t *p, int where)
 {
     SGM_TRY(require_init());
     if (!A || !p) return fail(SGM_ERR_BAD_ARG, "sgm_mat_left_permute: null argument");
+    if (A->fmt == SGM_FMT_ELL && !A->distributed()) SGM_TRY(ell_need_degrees("sgm_mat_left_permute", A->parts[0]));
     A->version += 1;
     A->pattern_version += 1;
     if (A->fmt == SGM_FMT_CSR && A->comm) {          // over ranks: p is the GLOBAL permutation, the same on every rank (collective)
@@ -882,20 +887,22 @@ int sgm_mat_left_permute(sgm_mat A, const int32_t *p, int where)
         const size_t total = (size_t)n * pt.max_d;
         int32_t *ecol2 = nullptr, *edeg2 = nullptr;
         double *eval2 = nullptr;
+        uint8_t *ezero2 = nullptr;
         int rc = dalloc(&ecol2, std::max<size_t>(total, 1));
         if (rc == SGM_OK) rc = dalloc(&eval2, std::max<size_t>(total, 1));
         if (rc == SGM_OK && pt.edeg) rc = dalloc(&edeg2, (size_t)std::max(n, 1));
+        if (rc == SGM_OK && pt.ezero) rc = dalloc(&ezero2, std::max<size_t>(total, 1));
         if (rc == SGM_OK && n) {
             hipLaunchKernelGGL(k_ell_perm_rows, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, n, pt.max_d,
                                (const int32_t *)dp, (const int32_t *)pt.ecol, (const double *)pt.eval,
-                               (const int32_t *)pt.edeg, ecol2, eval2, edeg2);
+                               (const int32_t *)pt.edeg, (const uint8_t *)pt.ezero, ecol2, eval2, edeg2, ezero2);
             if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess)
                 rc = fail(SGM_ERR_HIP, "sgm_mat_left_permute: kernel failed");
         }
         dfree(dp);
-        if (rc != SGM_OK) { dfree(ecol2); dfree(eval2); dfree(edeg2); return rc; }
-        dfree(pt.ecol); dfree(pt.eval); dfree(pt.edeg);
-        pt.ecol = ecol2; pt.eval = eval2; pt.edeg = edeg2;
+        if (rc != SGM_OK) { dfree(ecol2); dfree(eval2); dfree(edeg2); dfree(ezero2); return rc; }
+        dfree(pt.ecol); dfree(pt.eval); dfree(pt.edeg); dfree(pt.ezero);
+        pt.ecol = ecol2; pt.eval = eval2; pt.edeg = edeg2; pt.ezero = ezero2;
         SGM_TRY(sgm_invalidate_transpose(A));
         return rebuild_ell_formats(pt);
     }
@@ -938,6 +945,7 @@ int sgm_mat_right_permute(sgm_mat A, const int32_t *p, int where)
 {
     SGM_TRY(require_init());
     if (!A || !p) return fail(SGM_ERR_BAD_ARG, "sgm_mat_right_permute: null argument");
+    if (A->fmt == SGM_FMT_ELL && !A->distributed()) SGM_TRY(ell_need_degrees("sgm_mat_right_permute", A->parts[0]));
     A->version += 1;
     A->pattern_version += 1;
     if (A->fmt == SGM_FMT_CSR && A->comm) {          // over ranks: p is the GLOBAL permutation, the same on every rank (collective)
@@ -954,7 +962,7 @@ int sgm_mat_right_permute(sgm_mat A, const int32_t *p, int where)
     SGM_TRY(stage_perm("sgm_mat_right_permute", A->ncol, p, where, &dp));
     if (A->fmt == SGM_FMT_ELL) {         // ellpack_graphs.f90:523-541
         const int64_t total = (int64_t)pt.n * pt.max_d;
-        if (total) hipLaunchKernelGGL(k_ell_perm_cols, dim3(vec_grid(total)), dim3(kBlock), 0, g_rt.stream, total, pt.ecol, (const int32_t *)dp);
+        if (total) hipLaunchKernelGGL(k_ell_perm_cols, dim3(vec_grid(total)), dim3(kBlock), 0, g_rt.stream, total, pt.ecol, (const uint8_t *)pt.ezero, (const int32_t *)dp);
         const bool ok = hipStreamSynchronize(g_rt.stream) == hipSuccess && hipGetLastError() == hipSuccess;
         dfree(dp);
         if (!ok) return fail(SGM_ERR_HIP, "sgm_mat_right_permute: kernel failed");

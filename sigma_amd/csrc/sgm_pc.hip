@@ -36,17 +36,18 @@ __global__ void k_jacobi_setup_csr(int32_t count, int32_t row0, int32_t dcol, co
 }
 __global__ void k_jacobi_setup_ell(int32_t count, int32_t row0, int32_t dcol, int32_t n, int32_t max_d,
                                    const int32_t *__restrict__ ecol, const double *__restrict__ eval,
-                                   double *__restrict__ idiag)
+                                   const int32_t *__restrict__ edeg, double *__restrict__ idiag)
 {
     int32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= count) return;
     const int32_t i = row0 + t, want = i + dcol;
-    // ellpack get_value scans the first degrees(i) slots (ellpack_matrices.f90:232-235);
-    // padding repeats the last real neighbour with val 0, real neighbours are unique, so
-    // the FIRST hit is the real slot.
+    // ellpack get_value scans the first degrees(i) slots and keeps the LAST hit (ellpack_matrices.f90:232-235): the padding,
+    // whatever it holds, is no entry, and of a column stored twice among the real slots the later one answers
+    // (edeg: validated against max_d when it came in, sgm_ell_set_degrees; null only when there is no slot at all)
+    const int32_t d = edeg ? min(edeg[i], max_d) : 0;
     double z = 0.0;
-    for (int32_t k = 0; k < max_d; ++k)
-        if (ecol[(int64_t)k * n + i] == want) { z = eval[(int64_t)k * n + i]; break; }
+    for (int32_t k = 0; k < d; ++k)
+        if (ecol[(int64_t)k * n + i] == want) z = eval[(int64_t)k * n + i];
     idiag[t] = 1.0 / z;
 }
 __global__ void k_fill_inf(int32_t count, double *idiag)
@@ -403,18 +404,20 @@ int sgm_pc_setup(sgm_pc pc, sgm_mat A)
 }
 
 // out[t] = 1 / A(row0 + t, row0 + t + dcol) for `count` rows of the leaf part p (see k_jacobi_setup_csr)
-static void jacobi_rows(const Part &p, int32_t fmt, int32_t row0, int32_t count, int32_t dcol, double *out)
+static int jacobi_rows(const Part &p, int32_t fmt, int32_t row0, int32_t count, int32_t dcol, double *out)
 {
     hipStream_t st = g_rt.stream;
     const int grid = (count + kBlock - 1) / kBlock;
-    if (!grid) return;
+    if (fmt == SGM_FMT_ELL) SGM_TRY(ell_need_degrees("Jacobi setup", p));
+    if (!grid) return SGM_OK;
     if (fmt == SGM_FMT_CSR) {
-        if (csr_need_arrays(p) != SGM_OK) return;
+        SGM_TRY(csr_need_arrays(p));
         hipLaunchKernelGGL(k_jacobi_setup_csr, dim3(grid), dim3(kBlock), 0, st, count, row0, dcol, p.rowptr, p.col, p.val, out);
         csr_release_arrays(p);
     } else
         hipLaunchKernelGGL(k_jacobi_setup_ell, dim3(grid), dim3(kBlock), 0, st, count, row0, dcol, p.n, p.max_d, p.ecol,
-                           p.eval, out);
+                           p.eval, (const int32_t *)p.edeg, out);
+    return SGM_OK;
 }
 
 // jacobi_setup only needs A%get_value(i,i) (jacobi_solvers.f90:59-61), which a composite answers from the block that
@@ -441,7 +444,7 @@ static int jacobi_setup_composite(sgm_pc pc, sgm_mat A)
                 hipLaunchKernelGGL(k_fill_inf, dim3((hi - lo + kBlock - 1) / kBlock), dim3(kBlock), 0, st, hi - lo, out);
                 continue;
             }
-            jacobi_rows(C->parts[0], C->fmt, lo - A->blk_row_ptr[it], hi - lo, A->blk_row_ptr[it] - A->blk_col_ptr[jt], out);
+            SGM_TRY(jacobi_rows(C->parts[0], C->fmt, lo - A->blk_row_ptr[it], hi - lo, A->blk_row_ptr[it] - A->blk_col_ptr[jt], out));
         }
     SGM_HIP(hipGetLastError());
     return finish();
@@ -458,7 +461,7 @@ static int jacobi_setup_parts(sgm_pc pc, sgm_mat A)
         const Part &p = A->parts[ip];
         if (!pc->parts[ip].idiag) SGM_TRY(dalloc(&pc->parts[ip].idiag, (size_t)p.n + 2));
         pc->parts[ip].n = p.n;
-        jacobi_rows(p, A->fmt, 0, p.n, 0, pc->parts[ip].idiag);
+        SGM_TRY(jacobi_rows(p, A->fmt, 0, p.n, 0, pc->parts[ip].idiag));
     }
     SGM_HIP(hipGetLastError());
     return finish();

@@ -216,23 +216,37 @@ inline int host_partition_rows_by_nnz(int32_t nrow, const int32_t *ptr, int32_t 
 
 
 // ------------------------------------------------------------------ ELLPACK degrees, rows of a permuted matrix
-// degrees(i) of an ELLPACK row as the reference holds it (ellpack_graphs.f90:14-21): add_edge / graph_build set the whole rest of
-// the row to the neighbour just added (`g%node(d+1:, i) = j`, :164,:394-397) and never store a neighbour twice, so the last slot
-// holds the last real neighbour and its FIRST occurrence is slot degrees(i); an empty row keeps node(:, i) = 0.  (The device twin
-// is k_ell_degrees, sgm_mat.hip.)  node: (max_d, n) as the Fortran holds it, 1-based.
+// degrees(i) of an ELLPACK row as the reference holds it (ellpack_graphs.f90:14-21), when the caller hands none in: add_edge /
+// graph_build set the whole rest of the row to the neighbour just added (`g%node(d+1:, i) = j`, :164,:394-397) and never store a
+// neighbour twice, so the last slot holds the last real neighbour and its FIRST occurrence is slot degrees(i); an empty row keeps
+// node(:, i) = 0.  Three row shapes are taken, and nothing else:
+//   * d distinct nonzero slots, every later slot equal to slot d (add_edge)                   -> d
+//   * all 0                                                                                   -> 0
+//   * d distinct nonzero slots, every later slot 0 (a caller's zero padding)                  -> d
+// Any other row (a column repeated among the head, a tail that is neither) is -1: the padding does not describe it, and the
+// handle then holds no degrees at all.  A row delete_edge has worked on (:418-481: shift left, last slot = its left neighbour)
+// can look like an add_edge row with one more neighbour, which no rule can tell apart -- those need sgm_ell_set_degrees.
+// (SGM_ELL_ROW_DEGREE_BODY is the one statement of the rule: here for the host, in k_ell_degrees, sgm_mat.hip, for the device.)
+// node: (max_d, n) as the Fortran holds it, 1-based.
+#define SGM_ELL_ROW_DEGREE_BODY                                                                                   \
+    int32_t z = 0;                                                                                                \
+    while (z < max_d && row[z] != 0) ++z;                                                                         \
+    int32_t d = z;                                                                                                \
+    if (z < max_d) {                                                                                              \
+        for (int32_t k = z + 1; k < max_d; ++k) if (row[k] != 0) return -1;                                       \
+    } else if (max_d) {                                                                                           \
+        const int32_t last = row[max_d - 1];                                                                      \
+        for (d = 1; row[d - 1] != last; ++d) {}                                                                   \
+        for (int32_t k = d; k < max_d; ++k) if (row[k] != last) return -1;                                        \
+    }                                                                                                             \
+    for (int32_t a = 1; a < d; ++a)                                                                               \
+        for (int32_t b = 0; b < a; ++b) if (row[a] == row[b]) return -1;                                          \
+    return d;
+inline int32_t ell_row_degree_host(const int32_t *row, int32_t max_d) { SGM_ELL_ROW_DEGREE_BODY }
 inline int host_ell_degrees_host(int32_t n, int32_t max_d, const int32_t *node, int32_t *deg)
 {
     if (n < 0 || max_d < 0 || (n && max_d && !node) || (n && !deg)) return fail(SGM_ERR_BAD_ARG, "sgm_ell_degrees_host: bad argument");
-    for (int32_t i = 0; i < n; ++i) {
-        int32_t d = 0;
-        if (max_d) {
-            const int32_t *row = node + (size_t)i * max_d;
-            const int32_t last = row[max_d - 1];
-            if (last != 0)
-                for (d = 1; d < max_d && row[d - 1] != last; ++d) {}
-        }
-        deg[i] = d;
-    }
+    for (int32_t i = 0; i < n; ++i) deg[i] = max_d ? ell_row_degree_host(node + (size_t)i * max_d, max_d) : 0;
     return SGM_OK;
 }
 // Rows [r0, r1) (0-based) of A%left_permute(p) (cs_matrices.f90:471-478: row i becomes row p(i), its entries in their stored

@@ -104,6 +104,15 @@ interface
         integer(c_int), value :: where
         integer(c_int) :: rc
     end function
+    ! degrees(n) of the graph behind an ELLPACK matrix: the first degrees(i) slots of row i are its entries
+    function sgm_ell_set_degrees(A, degrees, where) &
+            & bind(c, name='sgm_ell_set_degrees') result(rc)
+        import :: c_ptr, c_int, c_int32_t
+        type(c_ptr), value :: A
+        integer(c_int32_t), intent(in) :: degrees(*)
+        integer(c_int), value :: where
+        integer(c_int) :: rc
+    end function
     function sgm_ell_set_values(A, val, where) &
             & bind(c, name='sgm_ell_set_values') result(rc)
         import :: c_ptr, c_int, c_double
@@ -693,7 +702,8 @@ interface
         integer(c_int), value :: where
         integer(c_int) :: rc
     end function
-    function sgm_ell_create_dist(A, comm, row_starts, max_d, node, val, where) &
+    ! degrees: c_loc of this rank's degrees(n_local), or c_null_ptr = recovered from the padding
+    function sgm_ell_create_dist(A, comm, row_starts, max_d, node, val, degrees, where) &
             & bind(c, name='sgm_ell_create_dist') result(rc)
         import :: c_ptr, c_int, c_int32_t, c_int64_t, c_double
         type(c_ptr), intent(out) :: A
@@ -702,6 +712,7 @@ interface
         integer(c_int32_t), value :: max_d
         integer(c_int32_t), intent(in) :: node(*)
         real(c_double), intent(in) :: val(*)
+        type(c_ptr), value :: degrees
         integer(c_int), value :: where
         integer(c_int) :: rc
     end function
@@ -1386,6 +1397,8 @@ subroutine hip_ell_upload(A)
         call hip_check(sgm_ell_create(A%handle, int(A%nrow, c_int32_t), &
             & int(A%ncol, c_int32_t), int(A%max_d, c_int32_t), &
             & A%node, A%val, SGM_HOST))
+        ! the matrix's own degrees, always: what the padding tells is a guess (include/sigma_hip.h, sgm_ell_set_degrees)
+        if (A%nrow > 0) call hip_check(sgm_ell_set_degrees(A%handle, int(A%degrees, c_int32_t), SGM_HOST))
     elseif (A%values_dirty) then
         call hip_check(sgm_ell_set_values(A%handle, A%val, SGM_HOST))
     endif
