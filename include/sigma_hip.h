@@ -48,7 +48,9 @@ enum {
 };
 enum { SGM_HOST = 0, SGM_DEVICE = 1 };
 enum { SGM_FMT_CSR = 1, SGM_FMT_ELL = 2, SGM_FMT_COMPOSITE = 3 };
-enum { SGM_SOLVER_CG = 1, SGM_SOLVER_BICGSTAB = 2, SGM_SOLVER_GMRES = 3, SGM_SOLVER_MINRES = 4 };
+enum { SGM_SOLVER_CG = 1, SGM_SOLVER_BICGSTAB = 2, SGM_SOLVER_GMRES = 3, SGM_SOLVER_MINRES = 4, SGM_SOLVER_LSQR = 5 };
+/* why an LSQR solve ended (sgm_lsqr_info): the iteration cap, rnorm <= tolerance, arnorm <= normal_tolerance, a NaN */
+enum { SGM_LSQR_STOP_CAP = 0, SGM_LSQR_STOP_RESIDUAL = 1, SGM_LSQR_STOP_NORMAL = 2, SGM_LSQR_STOP_NAN = 3 };
 enum { SGM_PC_JACOBI = 1, SGM_PC_ILDU0 = 2 };
 #define SGM_PC_MG 3        /* multigrid V-cycle: made by sgm_mg_create (it needs its prolongations), not by sgm_pc_create */
 
@@ -124,7 +126,7 @@ int sgm_synchronize(void);
  *                          size k; 0 = modified Gram-Schmidt (k + 2 dependent passes and reductions, 4 k + 8 vector passes),
  *                          the checker.  (Round 4's blocked CGS-2 with the second projection applied -- three passes, three
  *                          reductions -- was 1265 it/s on C3 against 1644 and is gone.)
- *   "dot_order" (0)        how CG / BiCGStab / MINRES add up their dot products.  0 = tree order (per-workgroup partial sums,
+ *   "dot_order" (0)        how CG / BiCGStab / MINRES / LSQR add up their dot products.  0 = tree order (per-workgroup partial sums,
  *                          re-reduced in a fixed order): a legal order for the Fortran intrinsic, deterministic, the fast one.
  *                          1 = the order the reference build uses (amdflang -O2 turns dot_product into ONE accumulator fed
  *                          first element to last, cg_solvers.f90:131,135,140): every iterate, iteration count and residual is
@@ -550,6 +552,49 @@ int sgm_mg_aggregation_hierarchy(sgm_mat A, double theta, double smooth_omega, i
  *                        a number.  The solve stops AT that step: the step is not counted, x keeps the value it had before it,
  *                        the call returns SGM_OK (with or without a cap) and converged = 0; res2 is NaN, or the last
  *                        phibar*phibar for gamma == 0.
+ * sgm_lsqr_create     <- NO reference counterpart; LSQR (Paige-Saunders, Golub-Kahan bidiagonalisation): min |A x - b|_2 for a
+ *                        RECTANGULAR A (nrow = m, ncol = n, any shape and rank; x has n entries, b has m), optionally damped.
+ *                        One product with A and one with A^T per step, four work vectors (u^ of m, v^ and w of n entries, one of
+ *                        max(m, n)) beside x, a residual norm that never increases.  Single-GPU CSR and ELLPACK matrices, no
+ *                        preconditioner: sgm_solver_setup refuses composite, row-partitioned and distributed matrices and
+ *                        sgm_solver_solve a non-null pc (a right preconditioner needs M^-T), both with SGM_ERR_UNSUPPORTED.
+ *                        A^T is the cached explicit transpose of sgm_mat_matvec_t -- a SECOND COPY of the matrix in device
+ *                        memory, counted by sgm_mat_footprint's resident bytes -- built at setup and given A's current values
+ *                        at the start of every solve.  The contract (tests/lsqr_restated.py restates it) --
+ *                        every operation rounded on its own, every sqrt(a*a + b*b) exactly that expression (never hypot),
+ *                        `A u` the library's product, `A^T u` sgm_mat_matvec_t's (every entry summed in the scatter's order:
+ *                        source row ascending, then slot), `a.a` the solver's dot product (tree order; ONE accumulator fed
+ *                        first element to last with option "dot_order" = 1, and then every bit of the solve is pinned).
+ *                        Neither bidiagonalisation vector is normalised in memory (u^ = beta u, v^ = alpha v):
+ *                            u^ = b - A x ; beta = sqrt(u^.u^)              beta == 0: return (0 iterations, stop 1)
+ *                            z = A^T u^ ; v^(i) = (1.0/beta)*z(i) ; alpha = sqrt(v^.v^)      alpha == 0: return (0 iterations, stop 2)
+ *                            w(i) = (1.0/alpha)*v^(i) ; phibar = beta ; rhobar = alpha ; Psi = 0
+ *                            rnorm = beta ; arnorm = alpha*beta ; the two tests below
+ *                            step k = 1, 2, ... (while the max_iter cap allows):
+ *                                y = A v^ ; u^(i) = (1.0/alpha)*y(i) - (alpha/beta)*u^(i) ; beta' = sqrt(u^.u^)
+ *                                beta' != 0:  z = A^T u^ ; v^(i) = (1.0/beta')*z(i) - (beta'/alpha)*v^(i) ; alpha' = sqrt(v^.v^)
+ *                                beta' == 0:  alpha' = 0
+ *                                damp != 0:   rhobar1 = sqrt(rhobar*rhobar + damp*damp) ; c1 = rhobar/rhobar1 ; s1 = damp/rhobar1
+ *                                             psi = s1*phibar ; phibar = c1*phibar ; Psi = Psi + psi*psi
+ *                                otherwise    rhobar1 = rhobar
+ *                                rho = sqrt(rhobar1*rhobar1 + beta'*beta') ; c = rhobar1/rho ; s = beta'/rho ; theta = s*alpha'
+ *                                rhobar = -(c*alpha') ; phi = c*phibar ; phibar = s*phibar
+ *                                rnorm = sqrt(phibar*phibar + Psi) (fabs(phibar) with damp == 0)
+ *                                arnorm = (fabs(phibar)*alpha')*fabs(c)
+ *                                x(i) = x(i) + (phi/rho)*w(i)
+ *                                beta' != 0 and alpha' != 0:  w(i) = (1.0/alpha')*v^(i) - (theta/rho)*w(i)
+ *                                alpha = alpha' ; beta = beta' ; iterations += 1 ; history gets rnorm ; res2 = rnorm*rnorm
+ *                                stop 1 if beta' == 0 ; else stop 2 if alpha' == 0 ; else the two tests:
+ *                            tests:  stop 1 if not rnorm > tolerance ; else stop 2 if not arnorm > normal_tolerance
+ *                        Both tolerances are ABSOLUTE.  A solve always returns SGM_OK with a stop value (sgm_lsqr_info), except
+ *                        at the cap: stop 1 = rnorm <= tolerance, the system is solved as a compatible one; stop 2 = arnorm
+ *                        <= normal_tolerance, the least-squares solution (arnorm estimates |A^T r - damp^2 (x - x0)|_2); stop 0
+ *                        = the max_iter cap (SGM_ERR_NOT_CONVERGED, as for cg); stop 3 = u^.u^ or v^.v^ negative or not a number,
+ *                        or rho or the new phibar not a number -- that step stores nothing: it is not counted and x keeps the
+ *                        last finished iterate (res2 is NaN).  `converged` = stop 1 or 2.  1.0/beta' and 1.0/alpha' are never
+ *                        formed from a zero.  With an initial guess the damped problem is the one for the CORRECTION:
+ *                        min |A d - (b - A x0)|^2 + damp^2 |d|^2, x = x0 + d.  normal_tolerance and damp are creation
+ *                        parameters (NaN or negative: SGM_ERR_BAD_ARG), live through sgm_lsqr_set_params like the tolerance.
  * sgm_solver_setup    <- solver%setup(A): square check, work vectors, iterations = 0
  *                        cg_solvers.f90:52-90
  * sgm_solver_solve    <- solver%solve(A,x,b[,pc]): cg_solve :116-150, cg_solve_pc :155-194,
@@ -570,6 +615,9 @@ int sgm_cg_create(sgm_solver *out, double tolerance);
 int sgm_bicgstab_create(sgm_solver *out, double tolerance);
 int sgm_gmres_create(sgm_solver *out, double tolerance, int32_t restart);
 int sgm_minres_create(sgm_solver *out, double tolerance);
+int sgm_lsqr_create(sgm_solver *out, double tolerance, double normal_tolerance, double damp);
+int sgm_lsqr_set_params(sgm_solver s, double normal_tolerance, double damp);
+int sgm_lsqr_info(sgm_solver s, int32_t *stop, double *rnorm, double *arnorm);
 int sgm_solver_setup(sgm_solver s, sgm_mat A);
 int sgm_solver_set_max_iter(sgm_solver s, int64_t max_iter /* <= 0: unbounded */);
 int sgm_solver_set_tolerance(sgm_solver s, double tolerance);

@@ -15,6 +15,7 @@ hot path -- same names, argument meaning and error behaviour --
     solver = cg(tolerance)                     cg_solvers.f90:36-47
     solver = bicgstab(tolerance)               bicgstab_solvers.f90:37-48
     solver = gmres(tolerance, restart); solver = minres(tolerance)         extensions: GMRES(m); MINRES for symmetric indefinite A
+    solver = lsqr(tolerance, normal_tolerance, damp)                       extension: least squares with a rectangular A
     pc = jacobi(); pc = ldu(incomplete, level) jacobi_solvers.f90:23-31, ldu_solvers.f90:73-86
     pc = multigrid(P, omega, nu_pre, nu_post)  V-cycle on the Galerkin levels of the prolongations P (an extension)
                                                coarse="direct": the last level inverted at setup, applied as a dense product
@@ -1013,7 +1014,7 @@ class _Solver:
 
     def set_option(self, name, value):
         """sgm_solver_set_option: this solver's own "cg_small" / "bicgstab_small" / "krylov_graph" / "dot_order" (CG, BiCGStab,
-        MINRES) / "gmres_cgs2" (read at the next solve)."""
+        MINRES, LSQR) / "gmres_cgs2" (read at the next solve)."""
         self._opts[name] = int(value)
         if self._h:
             _ck(lib().sgm_solver_set_option(self._h, name.encode(), C.c_int(int(value))))
@@ -1134,6 +1135,60 @@ class minres_solver(_Solver):
         _ck(lib().sgm_minres_create(C.byref(self._h), C.c_double(self.tolerance)))
 
 
+class lsqr_solver(_Solver):
+    """LSQR (sgm_lsqr_create): x has A.ncol entries, b has A.nrow; tolerance, normal_tolerance and damp are live fields, sent
+    before every solve."""
+
+    def __init__(self, tolerance, normal_tolerance, damp):
+        super().__init__(tolerance)
+        self.normal_tolerance = self.tolerance if normal_tolerance is None else float(normal_tolerance)
+        self.damp = float(damp)
+
+    def _create(self):
+        _ck(lib().sgm_lsqr_create(C.byref(self._h), C.c_double(self.tolerance), C.c_double(self.normal_tolerance),
+                                  C.c_double(self.damp)))
+
+    def set_params(self, tolerance=None, normal_tolerance=None, damp=0.0):
+        """Without arguments: tolerance = normal_tolerance = 1e-16, damp = 0."""
+        super().set_params(tolerance)
+        self.normal_tolerance = self.tolerance if normal_tolerance is None else float(normal_tolerance)
+        self.damp = float(damp)
+        return self
+
+    def solve(self, A, x, b, pc=None, check=True):
+        """min |A x - b|_2 (damped: the correction to the initial guess, see sgm_lsqr_create): x holds the initial guess on
+        entry, the solution on exit.  With set_max_iter, hitting the cap raises unless check=False.  `pc` is there for the
+        signature of the other solvers only: the library refuses a preconditioner (SigmaError 8)."""
+        _need(x, A.ncol, "lsqr solve x"); _need(b, A.nrow, "lsqr solve b")
+        px, wx, _k1 = _arg(x, np.float64, writable=True)
+        pb, wb, _k2 = _arg(b, np.float64)
+        _ck(lib().sgm_solver_set_tolerance(self._h, C.c_double(float(self.tolerance))))
+        _ck(lib().sgm_lsqr_set_params(self._h, C.c_double(float(self.normal_tolerance)), C.c_double(float(self.damp))))
+        rc = lib().sgm_solver_solve(self._h, A._h, px, pb, pc._h if pc is not None else None, C.c_int(_same_where(wx, wb)))
+        if rc == 5 and not check:
+            return x
+        _ck(rc)
+        return x
+
+    def _lsqr_info(self):
+        stop, rn, arn = C.c_int32(0), C.c_double(0.0), C.c_double(0.0)
+        _ck(lib().sgm_lsqr_info(self._h, C.byref(stop), C.byref(rn), C.byref(arn)))
+        return stop.value, rn.value, arn.value
+
+    @property
+    def stop(self):
+        """why the last solve ended: 1 rnorm <= tolerance, 2 arnorm <= normal_tolerance, 0 the iteration cap, 3 a NaN"""
+        return self._lsqr_info()[0]
+
+    @property
+    def rnorm(self):
+        return self._lsqr_info()[1]
+
+    @property
+    def arnorm(self):
+        return self._lsqr_info()[2]
+
+
 def cg(tolerance=None):
     """cg(tolerance) factory (cg_solvers.f90:36-47); default tolerance 1e-16 (:106)."""
     return cg_solver(tolerance)
@@ -1156,6 +1211,18 @@ def minres(tolerance=1e-16):
     with set_option("dot_order", 1) the whole solve is pinned bit for bit.  A step that cannot be finished (the preconditioner
     is not positive definite, a NaN) ends the solve without raising: `converged` is then False."""
     return minres_solver(tolerance)
+
+
+def lsqr(tolerance=1e-16, normal_tolerance=None, damp=0.0):
+    """LSQR (Paige-Saunders) for min |A x - b|_2 with a rectangular A of any shape and rank, optionally Tikhonov-damped
+    (sgm_lsqr_create; include/sigma_hip.h states the contract).  Not in the reference.  Two ABSOLUTE tolerances: `tolerance` on
+    the residual norm estimate (stop 1: a compatible system is solved), `normal_tolerance` on the estimate of |A^T r|_2 (stop 2:
+    the least-squares solution); None = the value of `tolerance`.  From x = 0 the solution is the minimum-norm one.  Single-GPU
+    csr_matrix and ellpack_matrix operands, no preconditioner; the history holds rnorm = sqrt(res2); with
+    set_option("dot_order", 1) the whole solve is pinned bit for bit.  A NaN ends the solve without raising (stop 3).
+    The cached transpose inherits A's kernel options: on a grid-like operand A.set_option("ell_colblock", 0) before setup keeps
+    its product on the row kernels (profiles/lsqr/ measures the difference)."""
+    return lsqr_solver(tolerance, normal_tolerance, damp)
 
 
 # ------------------------------------------------------------------------------------ #

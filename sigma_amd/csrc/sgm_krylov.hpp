@@ -1,5 +1,5 @@
 // Shared by the Krylov translation units (sgm_solvers.hip: solver object, dots, C ABI; sgm_cg.hip; sgm_bicgstab.hip;
-// sgm_gmres.hip; sgm_minres.hip; sgm_lanczos.hip): the generic fused vector kernel and its launcher, the functors more than one loop uses,
+// sgm_gmres.hip; sgm_minres.hip; sgm_lsqr.hip; sgm_lanczos.hip): the generic fused vector kernel and its launcher, the functors more than one loop uses,
 // the solver object and the helpers every loop calls.  Kernels defined here are `static`: each unit launches its own copy.
 #pragma once
 #include "sgm_internal.hpp"
@@ -339,6 +339,14 @@ struct MinresDev {
     double st[2][8];
     int32_t fail;
 };
+// ---- LSQR ------------------------------------------------------------------------------
+// lives in device memory: the recurrence's scalars (sgm_lsqr.hip: LS_ALPHA ...), twice like MinresDev's, the two norms the stop
+// tests look at as of the last finished step, and why the solve ended (SGM_LSQR_STOP_*; 0: it has not)
+struct LsqrDev {
+    double st[2][8];
+    double rnorm, arnorm;
+    int32_t stop;
+};
 // ---- dot_order = 1: the reference's dot_product order -----------------------------------------------------
 // The pinned reference build (amdflang -O2, x86-64 without FMA) turns `dot_product(a, b)` into ONE accumulator that
 // starts at +0.0 and takes the individually rounded products a(i) * b(i) first element to last
@@ -436,6 +444,7 @@ struct PartWork {
     double *history = nullptr;
     GmresState *gmres = nullptr;
     MinresDev *minres = nullptr;
+    LsqrDev *lsqr = nullptr;
     double *V = nullptr;             // GMRES basis, (restart+1) x next
     int count[kNumPartials] = {0};   // producer grid of each partial array
 };
@@ -448,11 +457,15 @@ struct sgm_solver_s {
     int64_t hist_cap = 0;
     bool initialized = false;
     int32_t nn = 0;
+    int32_t nc = 0;                  // columns of the matrix given to setup (== nn for every solver but LSQR)
+    double normal_tolerance = 1e-16, damp = 0.0;     // LSQR: sgm_lsqr_create / sgm_lsqr_set_params
+    int32_t lsqr_stop = 0;           // LSQR: why the last solve ended (SGM_LSQR_STOP_*) and the two norms its tests looked at
+    double lsqr_rnorm = 0.0, lsqr_arnorm = 0.0;
     int64_t iterations = 0;          // accumulates across solves (cg_solvers.f90:72,145)
     int64_t last_iterations = 0;
     double res2 = 0.0;
     int32_t converged = 0;
-    int32_t breakdown = 0;           // MINRES: the last solve stopped at a step it could not finish (run_minres); not an error, not converged
+    int32_t breakdown = 0;           // MINRES, LSQR: the last solve stopped at a step it could not finish (run_minres, run_lsqr); not an error, not converged
     bool seq = false;                // this solve runs with dot_order = 1 (set by sgm_solver_solve from the option)
     int32_t *abort_dev = nullptr;    // the preconditioner's sticky abort word while its pipelined sweeps are in use (sgm_pc.hip)
     int32_t aborted = 0;             // ... as last read by read_state: nonzero = this solve's iterates are spoiled, stop and redo
@@ -540,12 +553,13 @@ void free_work(sgm_solver s);
 ScalarRef ref(sgm_solver s, size_t ip, int k);
 double *part(sgm_solver s, size_t ip, int k);
 int finish_dots(sgm_solver s, sgm_mat A, const int *ks, int nk, const int (*vecs)[2] = nullptr, bool use_flag = false,
-                int gen = INT32_MAX, double *const *halo_of = nullptr);
+                int gen = INT32_MAX, double *const *halo_of = nullptr, int64_t len = -1);
 int read_state(sgm_solver s, int *flag, int64_t *iters, double *res);
 bool graph_applies(sgm_solver s, sgm_mat A, sgm_pc pc);
 int run_cg(sgm_solver s, sgm_mat A, double *const *x, const double *const *b, sgm_pc pc);
 int run_bicgstab(sgm_solver s, sgm_mat A, double *const *x, const double *const *b, sgm_pc pc);
 int run_gmres(sgm_solver s, sgm_mat A, double *const *x, const double *const *b, sgm_pc pc);
 int run_minres(sgm_solver s, sgm_mat A, double *const *x, const double *const *b, sgm_pc pc);
+int run_lsqr(sgm_solver s, sgm_mat A, double *const *x, const double *const *b);
 
 }  // namespace sgm

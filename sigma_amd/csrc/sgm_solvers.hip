@@ -1,5 +1,5 @@
 // Device-resident Krylov loops for gfx950: CG / PCG (cg_solvers.f90:116-194), BiCGStab /
-// preconditioned BiCGStab (bicgstab_solvers.f90:124-237), GMRES(m) and MINRES (no reference
+// preconditioned BiCGStab (bicgstab_solvers.f90:124-237), GMRES(m), MINRES and LSQR (no reference
 // counterpart), plus the dot / axpy statements they are made of.
 //
 // Design: the whole `do while (dsqrt(res2) > tolerance)` loop runs on the GPU.
@@ -99,14 +99,17 @@ __global__ __launch_bounds__(kBlock) void k_reduce_set(ReduceSet rs)
 }
 
 
-int num_work_vectors(int kind) { return kind == SGM_SOLVER_CG ? 4 : kind == SGM_SOLVER_BICGSTAB ? 8 : kind == SGM_SOLVER_MINRES ? 7 : 3; }
+int num_work_vectors(int kind)
+{
+    return kind == SGM_SOLVER_CG || kind == SGM_SOLVER_LSQR ? 4 : kind == SGM_SOLVER_BICGSTAB ? 8 : kind == SGM_SOLVER_MINRES ? 7 : 3;
+}
 
 void free_work(sgm_solver s)
 {
     for (auto &w : s->work) {
         for (double *v : w.vec) dfree(v);
         dfree(w.partials); dfree(w.slots); dfree(w.flag); dfree(w.iters); dfree(w.res);
-        dfree(w.history); dfree(w.gmres); dfree(w.minres); dfree(w.V);
+        dfree(w.history); dfree(w.gmres); dfree(w.minres); dfree(w.lsqr); dfree(w.V);
     }
     s->work.clear();
     dfree(s->x_backup);
@@ -133,7 +136,10 @@ double *part(sgm_solver s, size_t ip, int k) { return s->work[ip].partials + (si
 // partitioned solve adds the same products in the same global order as the one-part solve.
 // `halo_of` (one extended vector per part, multi-part solves only): its boundary rows travel to the neighbours' halo slots in
 // the same step as the sums (halo_exchange_allreduce)
-int finish_dots(sgm_solver s, sgm_mat A, const int *ks, int nk, const int (*vecs)[2], bool use_flag, int gen, double *const *halo_of)
+// `len` (dot_order = 1 only): the length the dots are taken over where it is not the part's row count (LSQR's vectors of ncol
+// entries); the partial sums of the tree order carry their own count
+int finish_dots(sgm_solver s, sgm_mat A, const int *ks, int nk, const int (*vecs)[2], bool use_flag, int gen, double *const *halo_of,
+                int64_t len)
 {
     if (halo_of && s->seq) SGM_TRY(halo_exchange(A, halo_of, g_rt.stream));
     if (s->seq) {
@@ -153,12 +159,13 @@ int finish_dots(sgm_solver s, sgm_mat A, const int *ks, int nk, const int (*vecs
                     d[u].init = ip ? s->work[ip - 1].slots + k : (ranks && A->comm->rank > 0 ? w.slots + k : nullptr);
                     d[u].out = w.slots + k;
                 }
+                const int64_t nseq = len >= 0 ? len : w.n;
                 if (nd == 1) {
                     d[1] = d[0];
-                    hipLaunchKernelGGL((k_dot_seq<1>), dim3(1), dim3(kBlock), 0, g_rt.stream, w.n, d[0], d[1],
+                    hipLaunchKernelGGL((k_dot_seq<1>), dim3(1), dim3(kBlock), 0, g_rt.stream, nseq, d[0], d[1],
                                        use_flag ? (const int *)w.flag : nullptr, gen);
                 } else {
-                    hipLaunchKernelGGL((k_dot_seq<2>), dim3(1), dim3(kBlock), 0, g_rt.stream, w.n, d[0], d[1],
+                    hipLaunchKernelGGL((k_dot_seq<2>), dim3(1), dim3(kBlock), 0, g_rt.stream, nseq, d[0], d[1],
                                        use_flag ? (const int *)w.flag : nullptr, gen);
                 }
             }
@@ -271,6 +278,39 @@ int sgm_gmres_create(sgm_solver *out, double tolerance, int32_t restart)
 }
 int sgm_minres_create(sgm_solver *out, double tolerance) { return solver_create(out, SGM_SOLVER_MINRES, tolerance, 0); }
 
+// the two creation parameters of LSQR that are not options (a NaN or a negative value is refused)
+static int lsqr_params_ok(const char *fn, double normal_tolerance, double damp)
+{
+    if (!(normal_tolerance >= 0.0)) return fail(SGM_ERR_BAD_ARG, "%s: normal_tolerance is negative or NaN", fn);
+    if (!(damp >= 0.0)) return fail(SGM_ERR_BAD_ARG, "%s: damp is negative or NaN", fn);
+    return SGM_OK;
+}
+int sgm_lsqr_create(sgm_solver *out, double tolerance, double normal_tolerance, double damp)
+{
+    SGM_TRY(lsqr_params_ok("sgm_lsqr_create", normal_tolerance, damp));
+    SGM_TRY(solver_create(out, SGM_SOLVER_LSQR, tolerance, 0));
+    (*out)->normal_tolerance = normal_tolerance;
+    (*out)->damp = damp;
+    return SGM_OK;
+}
+// live like the tolerance: launch arguments of the loop kernels, read when a solve starts
+int sgm_lsqr_set_params(sgm_solver s, double normal_tolerance, double damp)
+{
+    if (!s || s->kind != SGM_SOLVER_LSQR) return fail(SGM_ERR_BAD_ARG, "sgm_lsqr_set_params: not an LSQR solver");
+    SGM_TRY(lsqr_params_ok("sgm_lsqr_set_params", normal_tolerance, damp));
+    s->normal_tolerance = normal_tolerance;
+    s->damp = damp;
+    return SGM_OK;
+}
+int sgm_lsqr_info(sgm_solver s, int32_t *stop, double *rnorm, double *arnorm)
+{
+    if (!s || s->kind != SGM_SOLVER_LSQR) return fail(SGM_ERR_BAD_ARG, "sgm_lsqr_info: not an LSQR solver");
+    if (stop) *stop = s->lsqr_stop;
+    if (rnorm) *rnorm = s->lsqr_rnorm;
+    if (arnorm) *arnorm = s->lsqr_arnorm;
+    return SGM_OK;
+}
+
 // solver%tolerance is a public field the reference's loops read at every solve (`do while( dsqrt(res2)>solver%tolerance )`,
 // cg_solvers.f90:133,175; bicgstab_solvers.f90:153) and set_params may be called again (cg_solvers.f90:95-111): the tolerance of
 // a handle is live.  It is a launch argument of the loop kernels, read when a solve starts; work vectors, `iterations` and the
@@ -287,7 +327,13 @@ int sgm_solver_setup(sgm_solver s, sgm_mat A)
 {
     SGM_TRY(require_init());
     if (!s || !A) return fail(SGM_ERR_BAD_ARG, "sgm_solver_setup: null argument");
-    if (A->nrow != A->ncol)     // cg_solvers.f90:61-65
+    const bool lsqr = s->kind == SGM_SOLVER_LSQR;
+    if (lsqr) {                 // rectangular operands are what it is for; it needs A^T as a matrix of its own
+        if (A->fmt == SGM_FMT_COMPOSITE || A->distributed())
+            return fail(SGM_ERR_UNSUPPORTED, "LSQR runs on a single-GPU CSR or ELLPACK matrix: composite, row-partitioned and "
+                                             "distributed matrices are not supported");
+        SGM_TRY(ensure_transpose(A));
+    } else if (A->nrow != A->ncol)     // cg_solvers.f90:61-65
         return fail(SGM_ERR_DIMS, "Cannot make a %s solver for a non-square matrix",
                     s->kind == SGM_SOLVER_CG ? "CG" : s->kind == SGM_SOLVER_BICGSTAB ? "BiCGStab" : s->kind == SGM_SOLVER_MINRES ? "MINRES" : "GMRES");
     if (s->kind == SGM_SOLVER_MINRES) {
@@ -298,6 +344,7 @@ int sgm_solver_setup(sgm_solver s, sgm_mat A)
                                              "row-partitioned and distributed matrices are not supported");
     }
     s->nn = A->nrow;
+    s->nc = A->ncol;
     s->iterations = 0;          // cg_solvers.f90:72
     s->multi = A->distributed();
     {
@@ -323,6 +370,7 @@ int sgm_solver_setup(sgm_solver s, sgm_mat A)
             SGM_TRY(dalloc(&w.iters, 1));
             SGM_TRY(dalloc(&w.res, 1));
             if (s->kind == SGM_SOLVER_MINRES) SGM_TRY(dalloc(&w.minres, 1));
+            if (lsqr) SGM_TRY(dalloc(&w.lsqr, 1));
             if (s->kind == SGM_SOLVER_GMRES) {
                 SGM_TRY(dalloc(&w.gmres, 1));
                 SGM_TRY(dalloc(&w.V, (size_t)(s->restart + 1) * w.next + 2));
@@ -371,15 +419,19 @@ int sgm_solver_solve(sgm_solver s, sgm_mat A, double *x, const double *b, sgm_pc
     SGM_TRY(require_init());
     if (!s || !A || !x || !b) return fail(SGM_ERR_BAD_ARG, "sgm_solver_solve: null argument");
     if (!s->initialized) return fail(SGM_ERR_BAD_ARG, "sgm_solver_solve: solver%%setup(A) has not been called");
-    if (A->nrow != s->nn || s->work.size() != A->parts.size())
+    const bool lsqr = s->kind == SGM_SOLVER_LSQR;
+    if (A->nrow != s->nn || (lsqr && A->ncol != s->nc) || s->work.size() != A->parts.size())
         return fail(SGM_ERR_DIMS, "sgm_solver_solve: matrix does not match the one given to setup");
     const size_t P = A->parts.size();
     // the caller's vectors: global length for a single / in-process-partitioned matrix,
     // owned slice for a matrix distributed over processes
-    const int64_t nvec = A->comm ? A->parts[0].n : A->nrow;
+    if (lsqr && pc)
+        return fail(SGM_ERR_UNSUPPORTED, "sgm_solver_solve: LSQR takes no preconditioner (a right preconditioner needs M^-T)");
+    // (LSQR: x has ncol entries and b nrow; every other solver's matrix is square)
+    const int64_t nvec = A->comm ? A->parts[0].n : lsqr ? A->ncol : A->nrow;
     Staged sx, sb;
     SGM_TRY(stage_in(sx, x, nvec, where, true));
-    SGM_TRY(stage_in(sb, b, nvec, where, true));
+    SGM_TRY(stage_in(sb, b, lsqr ? (int64_t)A->nrow : nvec, where, true));
     std::vector<double *> xs(P);
     std::vector<const double *> bs(P);
     for (size_t ip = 0; ip < P; ++ip) {
@@ -434,6 +486,7 @@ int sgm_solver_solve(sgm_solver s, sgm_mat A, double *x, const double *b, sgm_pc
         if (s->kind == SGM_SOLVER_CG) rc = run_cg(s, Arun, xs.data(), bs.data(), pc);
         else if (s->kind == SGM_SOLVER_BICGSTAB) rc = run_bicgstab(s, Arun, xs.data(), bs.data(), pc);
         else if (s->kind == SGM_SOLVER_MINRES) rc = run_minres(s, Arun, xs.data(), bs.data(), pc);
+        else if (lsqr) rc = run_lsqr(s, Arun, xs.data(), bs.data());
         else rc = run_gmres(s, Arun, xs.data(), bs.data(), pc);
         if (rc != SGM_OK) return rc;
         if (!s->aborted) break;
@@ -478,7 +531,8 @@ int sgm_solver_solve(sgm_solver s, sgm_mat A, double *x, const double *b, sgm_pc
     const bool gmres_nan = s->kind == SGM_SOLVER_GMRES && s->res2 != s->res2;
     // MINRES: a step that could not be finished (M not positive definite, gamma == 0, a NaN) ends the solve with SGM_OK and
     // converged = 0, capped or not; only the cap itself is SGM_ERR_NOT_CONVERGED
-    const bool minres_end = s->kind == SGM_SOLVER_MINRES && s->breakdown;
+    // (LSQR: the same for a NaN, stop 3)
+    const bool minres_end = (s->kind == SGM_SOLVER_MINRES || lsqr) && s->breakdown;
     if ((s->max_iter > 0 || gmres_nan) && !s->converged && !minres_end) {
         if (s->res2 != s->res2) fail(SGM_ERR_NOT_CONVERGED, "solver broke down after %lld iterations (res2 is NaN)", (long long)s->last_iterations);
         else fail(SGM_ERR_NOT_CONVERGED, "solver stopped at max_iter=%lld with sqrt(res2)=%g > %g",

@@ -12,7 +12,8 @@
 !     linear_operator_interface.f90:185-194                                !
 !   cg(tol), bicgstab(tol)  cg_solvers.f90:36 hip_cg(tol), hip_bicgstab()  !
 !   (nothing: extensions)                     hip_gmres(tol, restart),     !
-!                                               hip_minres(tol)            !
+!                                               hip_minres(tol),           !
+!                                               hip_lsqr(tol, ntol, damp)  !
 !   jacobi(), ldu()     jacobi_solvers.f90:23 hip_jacobi(), hip_ldu()      !
 !   solver%setup(A), solver%solve(A,x,b[,pc]), solver%destroy()            !
 !   solver%iterations, %tolerance, %nn, %initialized                       !
@@ -379,6 +380,28 @@ interface
         import :: c_ptr, c_int, c_double
         type(c_ptr), intent(out) :: s
         real(c_double), value :: tolerance
+        integer(c_int) :: rc
+    end function
+    function sgm_lsqr_create(s, tolerance, normal_tolerance, damp) &
+            & bind(c, name='sgm_lsqr_create') result(rc)
+        import :: c_ptr, c_int, c_double
+        type(c_ptr), intent(out) :: s
+        real(c_double), value :: tolerance, normal_tolerance, damp
+        integer(c_int) :: rc
+    end function
+    function sgm_lsqr_set_params(s, normal_tolerance, damp) &
+            & bind(c, name='sgm_lsqr_set_params') result(rc)
+        import :: c_ptr, c_int, c_double
+        type(c_ptr), value :: s
+        real(c_double), value :: normal_tolerance, damp
+        integer(c_int) :: rc
+    end function
+    function sgm_lsqr_info(s, stop, rnorm, arnorm) &
+            & bind(c, name='sgm_lsqr_info') result(rc)
+        import :: c_ptr, c_int, c_int32_t, c_double
+        type(c_ptr), value :: s
+        integer(c_int32_t), intent(out) :: stop
+        real(c_double), intent(out) :: rnorm, arnorm
         integer(c_int) :: rc
     end function
     function sgm_solver_setup(s, A) bind(c, name='sgm_solver_setup') result(rc)
@@ -982,8 +1005,14 @@ type :: hip_linear_solver                                                  !
     logical :: initialized = .false.
     integer :: iterations = 0
     real(dp) :: tolerance = 1.0d-16
-    integer :: kind = 0          ! 1 cg, 2 bicgstab, 3 gmres, 4 minres, 11 jacobi, 12 ldu
+    integer :: kind = 0          ! 1 cg, 2 bicgstab, 3 gmres, 4 minres, 5 lsqr, 11 jacobi, 12 ldu
     integer :: restart = 30
+    ! LSQR (hip_lsqr): the second tolerance and the damping, live like `tolerance`; after a solve why it ended
+    ! (1 rnorm <= tolerance, 2 arnorm <= normal_tolerance, 0 the iteration cap, 3 a NaN) and the two norms
+    real(dp) :: normal_tolerance = 1.0d-16
+    real(dp) :: damp = 0.0d0
+    integer :: stop = 0
+    real(dp) :: rnorm = 0.0d0, arnorm = 0.0d0
     type(c_ptr) :: handle = c_null_ptr
 contains
     procedure :: setup => hip_solver_setup
@@ -1450,6 +1479,19 @@ function hip_minres(tolerance) result(s)          ! no reference counterpart: sy
     if (present(tolerance)) s%tolerance = tolerance
 end function
 
+function hip_lsqr(tolerance, normal_tolerance, damp) result(s)
+    ! no reference counterpart: min |A x - b|_2 for a rectangular A (x of ncol, b of nrow entries), optionally damped
+    ! (sgm_lsqr_create); normal_tolerance defaults to the tolerance; no preconditioner
+    real(dp), intent(in), optional :: tolerance, normal_tolerance, damp
+    type(hip_linear_solver), pointer :: s
+    allocate(s)
+    s%kind = 5
+    if (present(tolerance)) s%tolerance = tolerance
+    s%normal_tolerance = s%tolerance
+    if (present(normal_tolerance)) s%normal_tolerance = normal_tolerance
+    if (present(damp)) s%damp = damp
+end function
+
 function hip_jacobi() result(s)                    ! jacobi_solvers.f90:23-31
     type(hip_linear_solver), pointer :: s
     allocate(s)
@@ -1582,6 +1624,8 @@ subroutine hip_solver_make_handle(s)
         call hip_check(sgm_gmres_create(s%handle, s%tolerance, int(s%restart, c_int32_t)))
     case (4)
         call hip_check(sgm_minres_create(s%handle, s%tolerance))
+    case (5)
+        call hip_check(sgm_lsqr_create(s%handle, s%tolerance, s%normal_tolerance, s%damp))
     case (11)
         call hip_check(sgm_pc_create(s%handle, 1_c_int32_t))
     case (12)
@@ -1670,10 +1714,20 @@ subroutine hip_solver_solve_handle(s, Ah, x, b, pch)
     endif
     ! s%tolerance is live: the reference's loop reads the field at every solve (cg_solvers.f90:133)
     call hip_check(sgm_solver_set_tolerance(s%handle, s%tolerance))
+    if (s%kind == 5) call hip_check(sgm_lsqr_set_params(s%handle, s%normal_tolerance, s%damp))
     rc = sgm_solver_solve(s%handle, Ah, x, b, pch, SGM_HOST)
     if (rc /= 5) call hip_check(rc)         ! 5 = stopped at the set_max_iter extension: the caller reads %iterations
     call hip_check(sgm_solver_info(s%handle, its, res2, conv, last))
     s%iterations = int(its)
+    if (s%kind == 5) call hip_lsqr_read_info(s)
+end subroutine
+
+subroutine hip_lsqr_read_info(s)
+    class(hip_linear_solver), intent(inout) :: s
+    integer(c_int32_t) :: st
+    real(c_double) :: rn, arn
+    call hip_check(sgm_lsqr_info(s%handle, st, rn, arn))
+    s%stop = int(st); s%rnorm = real(rn, dp); s%arnorm = real(arn, dp)
 end subroutine
 
 subroutine hip_solver_set_params(s, tolerance)
@@ -1722,10 +1776,12 @@ subroutine hip_solver_solve_device(s, A, x, b, pc)
     if (present(pc)) hp = pc%handle
     call A%upload()
     call hip_check(sgm_solver_set_tolerance(s%handle, s%tolerance))
+    if (s%kind == 5) call hip_check(sgm_lsqr_set_params(s%handle, s%normal_tolerance, s%damp))
     rc = sgm_solver_solve(s%handle, A%handle, x%view, b%view, hp, SGM_DEVICE)
     if (rc /= 5) call hip_check(rc)
     call hip_check(sgm_solver_info(s%handle, its, res2, conv, last))
     s%iterations = int(its)
+    if (s%kind == 5) call hip_lsqr_read_info(s)
 end subroutine
 
 subroutine hip_dvec_alloc(v, n)
