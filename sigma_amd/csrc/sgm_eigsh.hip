@@ -15,11 +15,10 @@
 //     q_{j+1} = w * (1.0 / beta_j)                                FEigScale
 // -- three reads of the j + 1 columns and five passes over w, whatever j is.  Nothing in a cycle waits for the host: the step
 // kernel raises a device flag at an invariant subspace (or a NaN) and every later kernel of the cycle returns at once.
-// (k_egs, k_eig_reduce, k_basis_rotate, FEigScale and FEigResid are in sgm_eigsh_device.hpp: sgm_davidson.hip uses them too.)
+// (k_egs, k_eig_reduce, k_basis_rotate, FEigScale, FEigResid and the end of the call, eig_hand_back, are in
+// sgm_eigsh_device.hpp, the Rayleigh-Ritz block of a cycle, rayleigh_ritz, in sgm_symeig_host.hpp: sgm_davidson.hip uses them too.)
 #include "sgm_eigsh_device.hpp"
 #include "sgm_symeig_host.hpp"
-
-#include <numeric>
 
 namespace sgm {
 
@@ -139,7 +138,7 @@ int sgm_eigsh(sgm_mat A, int32_t k, int32_t ncv, int32_t which, double tol, int3
         SGM_HIP(hipStreamSynchronize(st));                        // (the staged copy of q1 is released here)
     }
 
-    std::vector<double> H((size_t)m * m, 0.0), Hb, theta(m), Z((size_t)m * m), Zsel((size_t)m * m);
+    std::vector<double> H((size_t)m * m, 0.0), theta(m), Z((size_t)m * m), Zsel((size_t)m * m);
     std::vector<int> order(m);
     EigDev hd;
     const int keep = std::min(k + (m - k) / 2, m - 1);
@@ -171,18 +170,10 @@ int sgm_eigsh(sgm_mat A, int32_t k, int32_t ncv, int32_t which, double tol, int3
             if (j + 1 < nc) H[(j + 1) + (size_t)j * m] = H[j + (size_t)(j + 1) * m] = hd.beta[j];
         }
         if (nan) break;
-        Hb.assign((size_t)nc * nc, 0.0);                          // the leading nc x nc block (nc < m only when the space has closed)
-        for (int jc = 0; jc < nc; ++jc)
-            for (int i = 0; i < nc; ++i) Hb[i + (size_t)jc * nc] = H[i + (size_t)jc * m];
-        symeig_jacobi(nc, Hb.data(), theta.data(), Z.data());
-        for (int i = 0; i < nc; ++i) {
-            if (theta[i] != theta[i]) nan = true;
-            if (fabs(theta[i]) > anorm) anorm = fabs(theta[i]);
-        }
+        // the leading nc x nc block (nc < m only when the space has closed), wanted end first
+        nan = !rayleigh_ritz(nc, H.data(), m, theta.data(), Z.data(), order.data(), anorm,
+                             [&](double a, double c2) { return which == 0 ? a < c2 : a > c2; });
         if (nan) break;
-        std::iota(order.begin(), order.begin() + nc, 0);
-        std::stable_sort(order.begin(), order.begin() + nc,
-                         [&](int a, int c2) { return which == 0 ? theta[a] < theta[c2] : theta[a] > theta[c2]; });
         if (closed) {                                             // an invariant subspace: every Ritz pair in it is exact, rho = 0
             found = std::min<int>(k, nc);
             converged = nc >= k;
@@ -210,31 +201,17 @@ int sgm_eigsh(sgm_mat A, int32_t k, int32_t ncv, int32_t which, double tol, int3
         ++restarts;                                               // (Zsel is next written after the next cycle's synchronisation)
     }
 
-    const double qnan = std::nan("");
-    for (int i = 0; i < k; ++i) lambda_out[i] = resid_out[i] = qnan;
     if (nan) found = 0, converged = 0;
-    if (found > 0) {
-        // V = Q[:, 0..nc-1] Z[:, wanted] ; resid_i = sqrt(r.r), r = A v_i - lambda_i v_i
-        for (int i = 0; i < found; ++i)
-            for (int r = 0; r < nc; ++r) Zsel[r + (size_t)i * nc] = Z[r + (size_t)order[i] * nc];
-        SGM_HIP(hipMemcpyAsync(b.Z, Zsel.data(), (size_t)nc * found * 8, hipMemcpyHostToDevice, st));
-        SGM_HIP(hipMemsetAsync(&b.S->flag, 0, sizeof(int32_t), st));
-        launch_rotate(n, nc, found, b.Q, ld, b.Z);
-        for (int i = 0; i < found; ++i) {
-            lambda_out[i] = theta[order[i]];
-            ++products;
-            SGM_TRY(product(q(i), b.w, nullptr));
-            launch_elem(n, FEigResid{b.w, q(i), lambda_out[i], b.parts + (size_t)i * kMaxGrid}, nullptr);
-        }
-        hipLaunchKernelGGL(k_eig_reduce, dim3(found), dim3(kBlock), 0, st, (const double *)b.parts, gd, rs, (const int *)nullptr);
-        SGM_HIP(hipGetLastError());
-        SGM_HIP(hipMemcpyAsync(resid_out, rs, (size_t)found * 8, hipMemcpyDeviceToHost, st));
-        if (V_out)
-            SGM_HIP(hipMemcpy2DAsync(V_out, (size_t)n * 8, b.Q, (size_t)ld * 8, (size_t)n * 8, found,
-                                     where == SGM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
-        SGM_HIP(hipStreamSynchronize(st));
-        for (int i = 0; i < found; ++i) resid_out[i] = sqrt(resid_out[i]);
-    }
+    // V = Q[:, 0..nc-1] Z[:, wanted] ; resid_i = sqrt(r.r), r = A v_i - lambda_i v_i
+    for (int i = 0; i < found; ++i)
+        for (int r = 0; r < nc; ++r) Zsel[r + (size_t)i * nc] = Z[r + (size_t)order[i] * nc];
+    if (found > 0) SGM_HIP(hipMemsetAsync(&b.S->flag, 0, sizeof(int32_t), st));
+    SGM_TRY(eig_hand_back(n, ld, nc, k, found, b.Q, Zsel.data(), b.Z, theta.data(), order.data(), b.parts, rs, lambda_out, V_out,
+                          resid_out, where, [&](const double *v, const double *&y, const double *&x) {
+                              ++products;
+                              y = b.w; x = v;
+                              return product(v, b.w, nullptr);
+                          }));
     info[0] = restarts;
     info[1] = products;
     info[2] = found;

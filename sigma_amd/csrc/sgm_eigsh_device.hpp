@@ -1,8 +1,9 @@
 // Shared by the eigensolver translation units (sgm_eigsh.hip: thick-restart Lanczos, sgm_basis_rotate; sgm_davidson.hip:
-// generalized Davidson; sgm_davidson_gen.hip: the same for A x = lambda B x): the passes over a basis resident in HBM --
-// classical Gram-Schmidt with its dots, the re-reduction of their partial sums, the in-place rotation by a small matrix --
-// the two functors the loops end with, and what a Davidson step leaves for the host.  One definition, a copy per file (the
-// library is built without relocatable device code): the non-template kernels are `static`.
+// generalized Davidson for A x = lambda x and A x = lambda B x): the passes over a basis resident in HBM -- classical
+// Gram-Schmidt with its dots, the re-reduction of their partial sums, the in-place rotation by a small matrix -- with_width,
+// the one place where a column count picks a kernel's width, the two functors the loops end with, eig_hand_back, the end of
+// every call (Ritz vectors, true residuals, the copies out), and what a Davidson step leaves for the host.  One definition, a
+// copy per file (the library is built without relocatable device code): the non-template kernels are `static`.
 #pragma once
 #include "sgm_krylov.hpp"
 
@@ -135,8 +136,7 @@ struct FEigResid {
     __device__ void finish(double *red) { put_partial(s, part, red); }
 };
 
-// What a Davidson step leaves for the host (sgm_davidson.hip, sgm_davidson_gen.hip); lives in device memory and is read
-// with H's new column
+// What a Davidson step leaves for the host (sgm_davidson.hip); lives in device memory and is read with H's new column
 struct DavDev {
     double tau;                    // sqrt(t.t) before the orthogonalisation
     double beta;                   // sqrt(t.t) after it
@@ -188,23 +188,65 @@ __global__ __launch_bounds__(kBlock) void k_basis_rotate(int64_t n, int m, int k
     }
 }
 
+// The width ladder: f is called once with Int<8 | 16 | 32 | 64>, the narrowest kernel width that holds m columns (m <= kEigMaxNcv;
+// Int<>: sgm_internal.hpp)
+template <class F> static void with_width(int m, F &&f)
+{
+    if (m <= 8) f(Int<8>{});
+    else if (m <= 16) f(Int<16>{});
+    else if (m <= 32) f(Int<32>{});
+    else f(Int<64>{});
+}
+
 static void launch_rotate(int64_t n, int m, int kk, double *Q, int64_t ldq, const double *Zdev)
 {
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n + kBlock - 1) / kBlock, 8192));
-    if (m <= 8) hipLaunchKernelGGL(k_basis_rotate<8>, dim3(grid), dim3(kBlock), 0, g_rt.stream, n, m, kk, Q, ldq, Zdev);
-    else if (m <= 16) hipLaunchKernelGGL(k_basis_rotate<16>, dim3(grid), dim3(kBlock), 0, g_rt.stream, n, m, kk, Q, ldq, Zdev);
-    else if (m <= 32) hipLaunchKernelGGL(k_basis_rotate<32>, dim3(grid), dim3(kBlock), 0, g_rt.stream, n, m, kk, Q, ldq, Zdev);
-    else hipLaunchKernelGGL(k_basis_rotate<64>, dim3(grid), dim3(kBlock), 0, g_rt.stream, n, m, kk, Q, ldq, Zdev);
+    with_width(m, [&](auto MB) {
+        hipLaunchKernelGGL(k_basis_rotate<decltype(MB)::value>, dim3(grid), dim3(kBlock), 0, g_rt.stream, n, m, kk, Q, ldq, Zdev);
+    });
 }
 
 template <int MODE>
 static void launch_egs(int64_t n, int kk, double *w, const double *Q, int64_t ldq, const double *coef, double *part, const int *flag)
 {
-    const dim3 grid(dot_grid(n)), block(kBlock);
-    if (kk <= 8) hipLaunchKernelGGL((k_egs<8, MODE>), grid, block, 0, g_rt.stream, n, kk, w, Q, ldq, coef, part, flag);
-    else if (kk <= 16) hipLaunchKernelGGL((k_egs<16, MODE>), grid, block, 0, g_rt.stream, n, kk, w, Q, ldq, coef, part, flag);
-    else if (kk <= 32) hipLaunchKernelGGL((k_egs<32, MODE>), grid, block, 0, g_rt.stream, n, kk, w, Q, ldq, coef, part, flag);
-    else hipLaunchKernelGGL((k_egs<64, MODE>), grid, block, 0, g_rt.stream, n, kk, w, Q, ldq, coef, part, flag);
+    with_width(kk, [&](auto KB) {
+        hipLaunchKernelGGL((k_egs<decltype(KB)::value, MODE>), dim3(dot_grid(n)), dim3(kBlock), 0, g_rt.stream, n, kk, w, Q, ldq, coef,
+                           part, flag);
+    });
+}
+
+// The end of a call.  lambda_out and resid_out (k each) are filled with NaN; with found > 0 then
+//     Q[:, 0:found] <- Q[:, 0:m] Zsel (m x found, the caller's selection) ; lambda_i = theta[order[i]]
+//     resid_i = sqrt(r.r), r = y - lambda_i x, where images(v_i, y, x) has launched what forms the pair's images and counted it
+//     (y = A v_i ; x = v_i, or B v_i)
+// -- one reduction of the `found` partial arrays in parts (re-reduced into rs), one synchronisation, the n x found block of Q
+// copied to V_out when there is one.
+template <class Images>
+static int eig_hand_back(int64_t n, int64_t ld, int m, int k, int found, double *Q, const double *Zsel, double *Zdev, const double *theta,
+                         const int *order, double *parts, double *rs, double *lambda_out, double *V_out, double *resid_out, int where,
+                         Images &&images)
+{
+    hipStream_t st = g_rt.stream;
+    const double qnan = std::nan("");
+    for (int i = 0; i < k; ++i) lambda_out[i] = resid_out[i] = qnan;
+    if (found <= 0) return SGM_OK;
+    SGM_HIP(hipMemcpyAsync(Zdev, Zsel, (size_t)m * found * 8, hipMemcpyHostToDevice, st));
+    launch_rotate(n, m, found, Q, ld, Zdev);
+    for (int i = 0; i < found; ++i) {
+        const double *y = nullptr, *x = nullptr;
+        lambda_out[i] = theta[order[i]];
+        SGM_TRY(images(Q + (size_t)i * ld, y, x));
+        launch_elem(n, FEigResid{y, x, lambda_out[i], parts + (size_t)i * kMaxGrid}, nullptr);
+    }
+    hipLaunchKernelGGL(k_eig_reduce, dim3(found), dim3(kBlock), 0, st, (const double *)parts, dot_grid(n), rs, (const int *)nullptr);
+    SGM_HIP(hipGetLastError());
+    SGM_HIP(hipMemcpyAsync(resid_out, rs, (size_t)found * 8, hipMemcpyDeviceToHost, st));
+    if (V_out)
+        SGM_HIP(hipMemcpy2DAsync(V_out, (size_t)n * 8, Q, (size_t)ld * 8, (size_t)n * 8, found,
+                                 where == SGM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
+    SGM_HIP(hipStreamSynchronize(st));
+    for (int i = 0; i < found; ++i) resid_out[i] = sqrt(resid_out[i]);
+    return SGM_OK;
 }
 
 }  // namespace sgm

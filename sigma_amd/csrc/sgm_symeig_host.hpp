@@ -1,5 +1,6 @@
 // Cyclic Jacobi for a small dense symmetric matrix, on the host: the eigensolver of sgm_eigsh's projected matrix H (after a
-// thick restart H is arrowhead plus tridiagonal, not tridiagonal) and the body of sgm_symeig_host.  Plain C++ without a HIP
+// thick restart H is arrowhead plus tridiagonal, not tridiagonal) and the body of sgm_symeig_host; and rayleigh_ritz, what
+// sgm_eigsh and the Davidson loop (sgm_davidson.hip) do with the leading block of their H.  Plain C++ without a HIP
 // call, so that a stand-alone program can run it under a host sanitizer (tools/symeig_host_check.cpp).  Must be compiled
 // with -ffp-contract=off: every operation below is rounded on its own, and tests/eigsh_restated.py restates it in numpy.
 //
@@ -18,8 +19,10 @@
 //             for every i:    x = Z(i,p) ; y = Z(i,q) ; Z(i,p) = c*x - s*y ; Z(i,q) = s*x + c*y
 //     theta(i) = A(i,i)          (in the order Jacobi leaves them: NOT sorted)
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <numeric>
 #include <vector>
 
 namespace sgm {
@@ -71,6 +74,29 @@ inline int32_t symeig_jacobi(int32_t m, const double *H, double *theta, double *
     }
     for (int32_t i = 0; i < m; ++i) theta[i] = a(i, i);
     return sweeps;
+}
+
+// Rayleigh-Ritz on the leading m x m block of H (column-major, leading dimension ldh), as sgm_eigsh and the Davidson loop take
+// it: theta and Z (m x m) from symeig_jacobi ; anorm = max(anorm, |theta_i|) ; order = 0 .. m-1 sorted by `before` on theta, equal
+// values in Jacobi's order.  false when an entry of the block or a theta is not a number: order is not written then.
+template <class Before>
+inline bool rayleigh_ritz(int32_t m, const double *H, int32_t ldh, double *theta, double *Z, int *order, double &anorm, Before before)
+{
+    std::vector<double> Hb((size_t)m * m);
+    for (int32_t jc = 0; jc < m; ++jc)
+        for (int32_t i = 0; i < m; ++i) {
+            const double h = H[i + (size_t)jc * ldh];
+            if (h != h) return false;
+            Hb[i + (size_t)jc * m] = h;
+        }
+    symeig_jacobi(m, Hb.data(), theta, Z);
+    for (int32_t i = 0; i < m; ++i) {
+        if (theta[i] != theta[i]) return false;
+        if (std::fabs(theta[i]) > anorm) anorm = std::fabs(theta[i]);
+    }
+    std::iota(order, order + m, 0);
+    std::stable_sort(order, order + m, [&](int a, int c) { return before(theta[a], theta[c]); });
+    return true;
 }
 
 }  // namespace sgm

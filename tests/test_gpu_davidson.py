@@ -2,7 +2,7 @@
 
   1  bit for bit: lam, V, residuals, steps, products, applies, restarts, found and converged equal the float64 restatement
      (tests/davidson_restated.py) run with the device's defined order of summation -- CSR, ELLPACK and composite matrices,
-     every preconditioner kind, k in {1, 4}, ncv in {8, 20}, host vectors and device tensors, a caller's q1;
+     every preconditioner kind, k in {1, 4}, ncv in {8, 20, 40}, host vectors and device tensors, a caller's q1;
   2  independent of the restatement: the analytic spectrum of the grid Laplacians (double eigenvalues included), the reported
      residual against one recomputed in longdouble, orthonormality;
   3  the V-cycle makes the step count grid-independent; 4 fewer products than sg.eigsh "SA" by a factor of 5 or more;
@@ -27,7 +27,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # (matrix, storage, preconditioner, k, ncv, device tensors, a caller's q1).  n = 957 (33 x 29: two 512-row slices, an odd
 # tail, one workgroup of partial sums), 300, 768 (the composite), 1845 (45 x 41: odd, two workgroups of partial sums);
 # ncv = 8 restarts 13 to 60 times, ncv = 20 two to seven times.  late40 (n = 40): a pair the space meets after two others have
-# been locked.
+# been locked.  ncv = 40: m passes 32, so k_dav_ritz<64>, k_egs<64, *> (columns not held) and k_basis_rotate<64> run -- spd300
+# restarts there twice (64 steps), odd reaches m = 33 without a restart (32 steps, the output rotation included).
 PINNED = [
     ("poisson33x29", "csr", "mg", 4, 20, False, False),
     ("poisson33x29", "csr", "mg", 4, 20, True, False),
@@ -39,6 +40,8 @@ PINNED = [
     ("comp32x24", "composite", "none", 1, 8, False, False),
     ("odd", "csr", "mg", 4, 20, False, True),
     ("late40", "csr", "none", 4, 20, False, False),
+    ("spd300", "csr", "none", 4, 40, False, False),
+    ("odd", "csr", "mg", 4, 40, False, False),
 ]
 PINNED_IDS = [f"{n}-{f}-{p}-k{k}-ncv{m}{'-tensor' if t else ''}{'-q1' if q else ''}" for n, f, p, k, m, t, q in PINNED]
 
