@@ -261,6 +261,45 @@ int sgm_mat_matvec_dots(sgm_mat A, const double *x, double *y, const double *w_o
  * column), x = this rank's owned rows, y = its owned columns.  Not available on in-process partitions.   */
 int sgm_mat_matvec_t(sgm_mat A, const double *x, double *y, int where);
 int sgm_mat_matvec_t_add(sgm_mat A, const double *x, double *y, int where);
+/* sgm_mat_matmat: Y = [Y +] op(A) X for a block of k vectors (an extension).
+ * Contract -- for every column j < k:
+ *   op = 0                          Y(:,j) holds exactly the bits sgm_mat_matvec would leave for x = X(:,j);
+ *   op = SGM_OP_ADD                 the bits of sgm_mat_matvec_add;
+ *   op = SGM_OP_TRANS [| SGM_OP_ADD] the bits of sgm_mat_matvec_t / sgm_mat_matvec_t_add, i.e. the chained sum over the cached
+ *                                   transpose (x length nrow, y length ncol).
+ * This holds for every matrix format, every kernel family and every setting of the matrix options; nothing else is promised
+ * about order.  X and Y are column-major with leading dimensions ldx and ldy (the layout of the eigensolvers' bases): column
+ * j starts at X + j * ldx / Y + j * ldy.  ldx must be at least the product's x length and ldy at least its y length.  Entries
+ * of Y between a column's last row and ldy are never written; without the add bit Y is never read; a NaN or Inf in one
+ * column of X reaches that column of Y only.
+ *   k == 0 is a no-op; k == 1 is the existing single-vector call; k < 0, bits of op other than the two above, a null pointer,
+ *   a short leading dimension, or overlapping address ranges of X and Y are SGM_ERR_BAD_ARG (Y untouched).
+ *   Host operands are staged as sgm_mat_matvec stages them; a device operand whose columns are not all 16-byte aligned (odd
+ *   leading dimension, odd base) is copied to an aligned block first, the rule a single vector is staged by.
+ *   Single-GPU CSR and ELLPACK matrices and composites of them are served; in-process partitions and matrices on a
+ *   communicator are SGM_ERR_UNSUPPORTED.
+ * What runs: the three sliced forms (k_csr_sl's 4-bit codes -- sliced ELLPACK included --, k_csr_slb's 1-byte codes,
+ * k_csr_sl32's int32 columns) have native multi-vector kernels (k_mm_sl / k_mm_slb / k_mm_sl32) that read the resident
+ * layout once per block of KB columns.  A call is cut, left to right, into blocks of the largest selected width that fits;
+ * a last single column goes through the existing product.  With the widths 8, 4 and 2 selected:
+ *   k = 2: 2    3: 2 + 1    4: 4    5: 4 + 1    6: 4 + 2    7: 4 + 2 + 1    8: 8    9: 8 + 1    15: 8 + 4 + 2 + 1
+ *   16: 8 + 8   17: 8 + 8 + 1   20: 8 + 8 + 4
+ * (which widths a form has is a measured decision, profiles/matmat/README.md; sgm_mat_matmat_kernel tells).  Every other
+ * layout (k_csr_do, k_csr_rl, k_csr_spmv, SELL, plain ELLPACK, k_ell_do, the column-blocked forms, composites) and a matrix
+ * whose slice_sched option is on run the column loop: one existing product per column.
+ *
+ * sgm_mat_matmat_kernel: what a call would run, without running it (like sgm_mat_kernel), e.g.
+ *   "k_mm_sl<W=5,KB=4> x1 + k_mm_sl<W=5,KB=2> x1 + k_csr_sl<W=5> x1", or "columns: k_csr_sell<...>" for the column loop.
+ *   (With SGM_OP_TRANS the cached transpose is built if it is not there yet.)
+ * sgm_mat_matmat_probe: test introspection -- the same product with the block width capped (block_cap = 1: the column loop;
+ *   0 = no cap) and the native kernels' grid capped at grid_cap workgroups (rounded down to a multiple of 8, at least 8;
+ *   0 = automatic).  Same bits whatever the caps.                                                                          */
+#define SGM_OP_ADD 1
+#define SGM_OP_TRANS 2
+int sgm_mat_matmat(sgm_mat A, int32_t op, int32_t k, const double *X, int64_t ldx, double *Y, int64_t ldy, int where);
+int sgm_mat_matmat_kernel(sgm_mat A, int32_t op, int32_t k, char *buf, int len);
+int sgm_mat_matmat_probe(sgm_mat A, int32_t op, int32_t k, const double *X, int64_t ldx, double *Y, int64_t ldy,
+                         int32_t block_cap, int32_t grid_cap, int where);
 /* sgm_csr_from_edges / sgm_ell_from_edges <- the assembly sequence of the reference's tests
  *   g%add_edge(i,j)... ; convert_graph_type(g, "compressed sparse" | "ellpack") ; A%set_graph(g) ;
  *   A%set_value(i,j,z)...        (test/solver_test_jacobi.f90:73-128)

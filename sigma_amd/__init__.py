@@ -180,6 +180,49 @@ def _need(a, n, what):
         raise SigmaError(2, f"{what}: vector has {_len(a)} entries, the operation needs {n}")
 
 
+OP_ADD, OP_TRANS = 1, 2        # SGM_OP_ADD, SGM_OP_TRANS (sgm_mat_matmat)
+
+
+def _block(B, n, what, writable=False):
+    """(pointer, where, k, ld, keepalive) for a block of k vectors of at least n entries, basis_rotate's convention: a numpy
+    array of shape (rows, k) whose columns are contiguous (Fortran order, or a view of the leading rows of such an array:
+    ld = the column stride), or a device tensor of shape (k, rows) whose rows are contiguous (ld = the row stride)."""
+    if _is_torch(B) and B.is_cuda:
+        import torch
+        if B.dim() != 2 or B.dtype != torch.float64 or (B.shape[1] > 1 and B.stride(1) != 1):
+            raise TypeError(f"{what}: a device block holds its columns as contiguous float64 rows: shape (k, n) expected")
+        k, rows = int(B.shape[0]), int(B.shape[1])
+        ld = int(B.stride(0)) if k > 1 else rows
+        if ld < rows:
+            raise TypeError(f"{what}: the rows of a device block must not overlap")
+        cur = torch.cuda.current_stream(B.device)
+        if cur.cuda_stream != _adopted_stream:
+            cur.synchronize()
+        ptr, where, keep = C.c_void_p(B.data_ptr()), SGM_DEVICE, B
+    else:
+        arr = B.numpy() if _is_torch(B) else np.asarray(B)
+        if arr.ndim != 2:
+            raise SigmaError(2, f"{what}: a block must have shape (n, k)")
+        k, rows = int(arr.shape[1]), int(arr.shape[0])
+        ok = arr.dtype == np.float64 and (rows <= 1 or arr.strides[0] == 8) and \
+            (k <= 1 or (arr.strides[1] % 8 == 0 and arr.strides[1] >= 8 * max(rows, 1)))
+        if not ok or (writable and not arr.flags.writeable):
+            if writable:
+                raise TypeError(f"{what}: the output block must be a writable float64 numpy array of shape (n, k) in Fortran order")
+            arr = np.asfortranarray(arr, np.float64)
+        ld = arr.strides[1] // 8 if k > 1 else max(rows, 1)
+        ptr, where, keep = C.c_void_p(arr.ctypes.data), SGM_HOST, arr
+    if rows < n:
+        raise SigmaError(2, f"{what}: the block's columns have {rows} entries, the operation needs {n}")
+    return ptr, where, k, max(ld, 1), keep
+
+
+def matmat_probe(A, X, Y, op=0, block_cap=0, grid_cap=0):
+    """sgm_mat_matmat_probe (test introspection): A.matmat & co. with the block width capped (block_cap = 1: the column loop,
+    0 = no cap) and the native kernels' grid capped at grid_cap workgroups (0 = automatic).  Same bits whatever the caps."""
+    return A._matmat(op, X, Y, "matmat_probe", block_cap=block_cap, grid_cap=grid_cap)
+
+
 def _same_where(*ws):
     if len(set(ws)) != 1:
         raise TypeError("all vectors of one call must live in the same place (host or device)")
@@ -258,6 +301,48 @@ class _Matrix:
         py, wy, _k2 = _arg(y, np.float64, writable=True)
         _ck(lib().sgm_mat_matvec_t_add(self._h, px, py, C.c_int(_same_where(wx, wy))))
         return y
+
+    # -- multi-vector products (an extension: sgm_mat_matmat, include/sigma_hip.h) ---------
+    def _matmat(self, op, X, Y, what, block_cap=None, grid_cap=0):
+        if hasattr(self, "_build"):
+            self._build()
+        trans = bool(op & OP_TRANS)
+        nx = getattr(self, "n_local", self.nrow) if trans else self._lens()[0]
+        ny = getattr(self, "nc_local", self.ncol) if trans else self._lens()[1]
+        px, wx, kx, ldx, _k1 = _block(X, nx, what + " X")
+        py, wy, ky, ldy, _k2 = _block(Y, ny, what + " Y", writable=True)
+        if kx != ky:
+            raise SigmaError(2, f"{what}: X holds {kx} columns, Y holds {ky}")
+        w = C.c_int(_same_where(wx, wy))
+        if block_cap is None:
+            _ck(lib().sgm_mat_matmat(self._h, C.c_int32(op), C.c_int32(kx), px, C.c_int64(ldx), py, C.c_int64(ldy), w))
+        else:
+            _ck(lib().sgm_mat_matmat_probe(self._h, C.c_int32(op), C.c_int32(kx), px, C.c_int64(ldx), py, C.c_int64(ldy),
+                                           C.c_int32(block_cap), C.c_int32(grid_cap), w))
+        return Y
+
+    def matmat(self, X, Y):
+        """Y = A X for a block of k vectors: column j of Y holds the bits matvec leaves for column j of X.  Blocks follow
+        basis_rotate's convention: a numpy array of shape (n, k) in Fortran order, or a device tensor of shape (k, n) that
+        holds the columns as contiguous rows."""
+        return self._matmat(0, X, Y, "matmat")
+
+    def matmat_add(self, X, Y):
+        return self._matmat(OP_ADD, X, Y, "matmat_add")
+
+    def matmat_t(self, X, Y):
+        return self._matmat(OP_TRANS, X, Y, "matmat_t")
+
+    def matmat_t_add(self, X, Y):
+        return self._matmat(OP_TRANS | OP_ADD, X, Y, "matmat_t_add")
+
+    def matmat_kernel(self, k, op=0):
+        """What matmat would run for k columns, without running it (sgm_mat_matmat_kernel)."""
+        if hasattr(self, "_build"):
+            self._build()
+        buf = C.create_string_buffer(512)
+        _ck(lib().sgm_mat_matmat_kernel(self._h, C.c_int32(op), C.c_int32(k), buf, C.c_int(512)))
+        return buf.value.decode()
 
     def halo_nbrs(self, part=0):
         """Exchange plan of local part `part` (parity checks): list of dicts with peer, send_count,

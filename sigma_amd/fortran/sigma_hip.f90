@@ -158,6 +158,37 @@ interface
         integer(c_int), value :: where
         integer(c_int) :: rc
     end function
+    function sgm_mat_matmat(A, op, k, X, ldx, Y, ldy, where) &
+            & bind(c, name='sgm_mat_matmat') result(rc)
+        import :: c_ptr, c_int, c_int32_t, c_int64_t, c_double
+        type(c_ptr), value :: A
+        integer(c_int32_t), value :: op, k
+        real(c_double), intent(in) :: X(*)
+        integer(c_int64_t), value :: ldx, ldy
+        real(c_double), intent(inout) :: Y(*)
+        integer(c_int), value :: where
+        integer(c_int) :: rc
+    end function
+    function sgm_mat_matmat_kernel(A, op, k, buf, len) &
+            & bind(c, name='sgm_mat_matmat_kernel') result(rc)
+        import :: c_ptr, c_int, c_int32_t, c_char
+        type(c_ptr), value :: A
+        integer(c_int32_t), value :: op, k
+        character(kind=c_char), intent(out) :: buf(*)
+        integer(c_int), value :: len
+        integer(c_int) :: rc
+    end function
+    function sgm_mat_matmat_probe(A, op, k, X, ldx, Y, ldy, block_cap, grid_cap, where) &
+            & bind(c, name='sgm_mat_matmat_probe') result(rc)
+        import :: c_ptr, c_int, c_int32_t, c_int64_t, c_double
+        type(c_ptr), value :: A
+        integer(c_int32_t), value :: op, k, block_cap, grid_cap
+        real(c_double), intent(in) :: X(*)
+        integer(c_int64_t), value :: ldx, ldy
+        real(c_double), intent(inout) :: Y(*)
+        integer(c_int), value :: where
+        integer(c_int) :: rc
+    end function
     function sgm_mat_left_permute(A, p, where) &
             & bind(c, name='sgm_mat_left_permute') result(rc)
         import
@@ -846,6 +877,10 @@ contains
     procedure :: matvec_add => hip_matrix_matvec_add
     procedure :: matvec_t => hip_matrix_matvec_t
     procedure :: matvec_t_add => hip_matrix_matvec_t_add
+    procedure :: matmat => hip_matmat
+    procedure :: matmat_add => hip_matmat_add
+    procedure :: matmat_t => hip_matmat_t
+    procedure :: matmat_t_add => hip_matmat_t_add
     procedure :: kernel_name => hip_matrix_kernel_name
     procedure :: set_option => hip_matrix_set_option
 end type hip_matrix
@@ -1185,6 +1220,50 @@ subroutine hip_matrix_matvec_t_add(A, x, y)  ! csc_matvec_add, cs_matrices.f90:6
     real(dp), intent(inout) :: y(:)
     call A%upload()
     call hip_check(sgm_mat_matvec_t_add(A%handle, x, y, SGM_HOST))
+end subroutine
+
+! multi-vector products (sgm_mat_matmat): column j of Y holds the bits the single-vector product leaves for column j of X;
+! X and Y contiguous, one vector per column, ld = size(., 1)
+subroutine hip_matmat_op(A, op, X, Y)
+    class(hip_matrix), intent(inout) :: A
+    integer, intent(in) :: op
+    real(dp), intent(in), contiguous :: X(:,:)
+    real(dp), intent(inout), contiguous :: Y(:,:)
+    if (size(X, 2) /= size(Y, 2)) then
+        print *, 'hip_matmat: X and Y hold different numbers of columns'
+        call exit(1)
+    endif
+    call A%upload()
+    call hip_check(sgm_mat_matmat(A%handle, int(op, c_int32_t), int(size(X, 2), c_int32_t), X, &
+        & int(size(X, 1), c_int64_t), Y, int(size(Y, 1), c_int64_t), SGM_HOST))
+end subroutine
+
+subroutine hip_matmat(A, X, Y)
+    class(hip_matrix), intent(inout) :: A
+    real(dp), intent(in), contiguous :: X(:,:)
+    real(dp), intent(inout), contiguous :: Y(:,:)
+    call hip_matmat_op(A, 0, X, Y)
+end subroutine
+
+subroutine hip_matmat_add(A, X, Y)
+    class(hip_matrix), intent(inout) :: A
+    real(dp), intent(in), contiguous :: X(:,:)
+    real(dp), intent(inout), contiguous :: Y(:,:)
+    call hip_matmat_op(A, 1, X, Y)
+end subroutine
+
+subroutine hip_matmat_t(A, X, Y)
+    class(hip_matrix), intent(inout) :: A
+    real(dp), intent(in), contiguous :: X(:,:)
+    real(dp), intent(inout), contiguous :: Y(:,:)
+    call hip_matmat_op(A, 2, X, Y)
+end subroutine
+
+subroutine hip_matmat_t_add(A, X, Y)
+    class(hip_matrix), intent(inout) :: A
+    real(dp), intent(in), contiguous :: X(:,:)
+    real(dp), intent(inout), contiguous :: Y(:,:)
+    call hip_matmat_op(A, 3, X, Y)
 end subroutine
 
 function hip_matrix_kernel_name(A) result(name)
